@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- depth-samples/s of the MVSNet hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 One step = one pass of the hot path over one batch of synthetic DTU-shaped input on every rank:
 BASELINE config 2 -- MVSNet (refine off), N=3 views, 640x512 images, D=192, fp32, forward + loss
-(mvsnet_loss, jdacs/models/mvsnet.py:164) + backward + gradient all-reduce (RCCL, N>1) + Adam step.
+(mvsnet_loss, jdacs/models/mvsnet.py:164) + backward + gradient all-reduce (RCCL, N>1) + Adam step, every step from the same
+parameters and optimiser state (restored in front of it: one copy, one memset).
 1 sample per GPU per step (weak scaling, like the reference's batch 1/GPU recipe, jdacs/train.sh).
-Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K
+steps and prints the line; --full adds the per-kernel / roofline figures, the other modes' timings and the CPU / stock-PyTorch
+baselines; --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -337,6 +340,32 @@ def calibrate_bn(net, *inputs):
     net.eval()
 
 
+DUMP_MAX_ELEMS = 1 << 21    # per array (8 MB of float32, at most 8 arrays); a larger output is written as a fixed, seeded sample of its elements
+
+
+def dump_outputs(folder, out, loss, bucket):
+    """--dump-outputs: what a caller of the timed path received from its last step, as float32 .npy files -- the model's output
+    dict and the loss; for the training configs also the all-reduced gradient bucket and the parameters the optimiser wrote."""
+    import numpy as np
+    arrays = {} if loss is None else {"loss": loss}
+    for k, v in out.items():
+        if isinstance(v, (list, tuple)):
+            arrays.update(("%s_%d" % (k, i), t) for i, t in enumerate(v))
+        else:
+            arrays[k] = v
+    if bucket is not None:
+        arrays["grad_bucket"] = bucket.flat
+        arrays["params"] = bucket.flat_param
+    os.makedirs(folder, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+            name += "_sample"
+        np.save(os.path.join(folder, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -396,7 +425,17 @@ def main():
                     help="launcher check (tests, no GPU needed): start the ranks, all-reduce one number over gloo, print it, exit")
     ap.add_argument("--time-all-kernels", action="store_true",
                     help="extra untimed pass bracketing EVERY C-ABI call with HIP events (diagnostics to stderr)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: HIP-event brackets of the roofline kernel inside the timed region, the passes "
+                         "after it (other tagged kernels, other weight-gradient modes, the opt-in split-bf16 step, the feature pyramid of "
+                         "--config 4), PMC traffic, conv0's weight gradient on all CUs, cpu_baseline and reference_gpu_path.  Without it "
+                         "the run sets up, warms up, times --steps steps, dumps its outputs if asked and prints the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps: write what the last timed step computed (depth, confidence, loss; for the training "
+                         "configs also the all-reduced gradient bucket and the updated parameters) as DIR/<name>.npy in float32.  Every step "
+                         "starts from the same state, so two runs agree to rounding (float atomics in the backward kernels)")
     args = ap.parse_args()
+    full = args.full
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks here (one process per GPU, the reference starts all its
@@ -481,6 +520,7 @@ def main():
     torch.manual_seed(0)
     train = cfg["kind"] in ("train", "selfsup")
     bucket = opt = None
+    last = {} if args.dump_outputs else None   # --dump-outputs: the outputs of the latest step (None: nothing is kept)
     if cfg["kind"] == "cvp_infer":
         from types import SimpleNamespace
         from mvs_amd.jdacs_ms.models.network import CVPMVSNet
@@ -499,6 +539,8 @@ def main():
         def fwd_bwd():
             with torch.no_grad():
                 out = net(*cvp_in)
+            if last is not None:
+                last["out"] = out
             return out["depth_est_list"][0].mean()
     else:
         net = MVSNet(refine=False, channels_last_features=bool(args.feature_channels_last))
@@ -537,6 +579,26 @@ def main():
             # capturable: the step counter lives on the GPU, so a captured optimizer step stays correct when replayed
             # (as 32 slices of the flat store: a fused multi-tensor optimiser runs one workgroup per tensor chunk)
             opt = torch.optim.Adam(bucket.optimizer_params(32), lr=1e-4, betas=(0.9, 0.999), fused=True, capturable=args.graph != 0)
+            # Every step starts from the same parameters and optimiser state, so a step's results are a function of the inputs
+            # alone.  Stepping on from the previous step's state instead, the last-bit differences of the float atomics in the
+            # backward kernels grow from step to step (the peaky softmax + Adam): two identical 25-step runs ended 470 mm apart
+            # in depth.  The optimiser state (exp_avg | exp_avg_sq | step of every slice) lives in ONE buffer, so the restore in
+            # front of each step is two launches: a 1.35 MB copy and a memset.
+            params0 = bucket.flat_param.detach().clone()
+            slices = opt.param_groups[0]["params"]
+            n_all = params0.numel()
+            opt_state = torch.zeros(2 * n_all + len(slices), dtype=torch.float32, device=dev)
+            off = 0
+            for i, p in enumerate(slices):
+                n = p.numel()
+                opt.state[p] = {"step": opt_state[2 * n_all + i], "exp_avg": opt_state[off:off + n].view_as(p),
+                                "exp_avg_sq": opt_state[n_all + off:n_all + off + n].view_as(p)}
+                off += n
+
+            def restore_state():
+                with torch.no_grad():
+                    bucket.flat_param.copy_(params0)
+                opt_state.zero_()
 
             phase_marks = [] if args.step_events else None     # diagnostics: host clock after forward+loss / backward, per step
 
@@ -547,6 +609,8 @@ def main():
                     loss = unsup(imgs, cams, out["depth"])          # jdacs/train.py:199-210 (standard unsupervised loss)
                 else:
                     loss = mvsnet_loss(out["depth"], gt, mask)
+                if last is not None:
+                    last["out"] = out
                 if phase_marks is not None:
                     phase_marks.append(time.perf_counter())
                 loss.backward()
@@ -562,9 +626,13 @@ def main():
             def fwd_bwd():
                 with torch.no_grad():
                     out = net(imgs, proj, dv)
+                if last is not None:
+                    last["out"] = out
                 return out["depth"].mean()
 
     def step():
+        if train:
+            restore_state()
         loss = fwd_bwd()
         if train:
             bucket.all_reduce()   # one RCCL all-reduce of the flat 1.35 MB bucket (no-op at world size 1)
@@ -611,6 +679,8 @@ def main():
                     opt.step()
 
             def step():  # noqa: F811
+                if train:
+                    restore_state()
                 graph_a.replay()
                 if train:
                     bucket.all_reduce()
@@ -645,8 +715,8 @@ def main():
     in_region = {k: v for k, v in tagmap.items() if dom_key is None or k == dom_key}
     later = {k: v for k, v in tagmap.items() if k not in in_region}
     timer = _lib.KernelTimer(only={t for _, t in in_region.values()}, names={n for n, _ in in_region.values()})
-    if not graph_mode:
-        lib.profiler = timer   # live HIP-event brackets inside the timed region (eager mode)
+    if not graph_mode and full:
+        lib.profiler = timer   # live HIP-event brackets inside the timed region (eager mode, --full)
     host_trace = None
     if args.step_events >= 2:
         class HostTrace:       # diagnostics: host clock at every C-ABI call of the timed steps (no HIP events)
@@ -690,7 +760,9 @@ def main():
     gc.enable()
     lib.profiler = None
     join_trace, _ops.JOIN_TRACE = _ops.JOIN_TRACE, None
-    if graph_mode:
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last["out"], loss if train else None, bucket)
+    if graph_mode and full:
         # kernels inside a graph replay cannot be bracketed by events; time the very same launches with HIP
         # events in an eager pass of the same K steps directly after the timed region (same process, same data)
         lib.profiler = timer
@@ -699,7 +771,7 @@ def main():
         torch.cuda.synchronize()
         lib.profiler = None
     timer2 = None
-    if later:
+    if later and full:
         # the other tagged kernels: the same K steps again (on every rank: a step holds the collective), bracketed, right after
         # the timed region (never part of `value`)
         timer2 = _lib.KernelTimer(only={t for _, t in later.values()}, names={n for n, _ in later.values()})
@@ -718,7 +790,7 @@ def main():
         per = sorted(float(t[0]) / args.steps * 1e3 for t in allt)
         multi["per_rank_ms_per_step"] = {"min": per[0], "median": per[len(per) // 2], "max": per[-1], "by_rank": [float(t[0]) / args.steps * 1e3 for t in allt]}
         multi["per_rank_host_enqueue_ms_per_step"] = [float(t[1]) / args.steps * 1e3 for t in allt]
-        if train:
+        if train and full:
             # the collective alone: 20 all-reduces of the flat gradient bucket back to back, HIP events on this rank (a per-link-bound
             # ring over xGMI moves 1.35 MB in tens of microseconds; what is measured here is launch + latency)
             evs = []
@@ -744,7 +816,7 @@ def main():
     ms_other_mode = None
     ms_library_default = None
     timer3 = None
-    if train and not graph_mode and async_wgrad and defer_join:
+    if full and train and not graph_mode and async_wgrad and defer_join:
         # the LIBRARY default (what the drop-in under the reference's own train.py gets): side-stream weight gradients joined INSIDE
         # the regulariser node, so every gradient autograd hands on is finished
         _ops.set_async_wgrad(True, defer_join=False)
@@ -761,7 +833,7 @@ def main():
         ms_library_default = float(tm.item()) / args.steps * 1e3
         _ops.set_async_wgrad(True, defer_join=True)
     ms_split_bf16 = None
-    if train and not graph_mode:
+    if full and train and not graph_mode:
         # OPT-IN arithmetic (knob conv0_x3 = 3, csrc/conv3d_x3.hip), never the headline: conv0's forward and input gradient on the bf16
         # MFMA with every fp32 operand split into three bf16 terms (six exact products per fp32 product, fp32 accumulation; measured
         # error against fp64 BELOW the fp32-MFMA kernels': tests/test_gpu_parity.py::test_conv0_*_split_bf16_form_vs_fp64)
@@ -782,7 +854,7 @@ def main():
         ms_split_bf16 = float(tm.item()) / args.steps * 1e3
         lib.call("mvs_set_tuning", b"conv0_x3", int(x3_before.value))
     ms_join_in_node = None
-    if train and not graph_mode and async_wgrad and not defer_join and _ops.TAIL_JOIN:
+    if full and train and not graph_mode and async_wgrad and not defer_join and _ops.TAIL_JOIN:
         # what the library default was in rounds 3-5 (MVS_TAIL_JOIN=0): the side stream joined INSIDE the regulariser node
         _ops.TAIL_JOIN = False
         for _ in range(2):
@@ -797,7 +869,7 @@ def main():
             dist.all_reduce(tm, op=dist.ReduceOp.MAX)
         ms_join_in_node = float(tm.item()) / args.steps * 1e3
         _ops.TAIL_JOIN = True
-    if train and not graph_mode:
+    if full and train and not graph_mode:
         _ops.set_async_wgrad(not async_wgrad)
         for _ in range(2):
             step()
@@ -971,7 +1043,7 @@ def main():
                                 "timed": "HIP events inside the timed region" if (name, tag) in summ
                                 else "HIP events, second pass of the same K steps after the timed region"}
         traffic, traffic_note = None, "not collected"
-        if args.pmc and world == 1:    # tools/pmc_driver.py replays this config's tagged kernels at this config's shapes
+        if full and args.pmc and world == 1:    # tools/pmc_driver.py replays this config's tagged kernels at this config's shapes
             try:
                 traffic, traffic_note = pmc_traffic(args.config, dtype)
             except Exception as e:  # the bench line must still come out
@@ -1009,7 +1081,7 @@ def main():
                 k3["frac_alone"] = work[dom_key][1] / (s3[1] * 1e-3) / 1e12 / MFMA_F32_PEAK_TFLOPS
                 k3["alone_is"] = ("the same launch in the synchronous-weight-gradient pass after the timed region (main stream, nothing "
                                   "beside it); `ms` / `frac` are its duration on the side stream, under the main stream's kernels")
-        if dom_key == "conv0_wgrad" and dom_key in kernels and train and world == 1:
+        if full and dom_key == "conv0_wgrad" and dom_key in kernels and train and world == 1:
             try:
                 kernels[dom_key].update(wgrad_all_cus(lib, dev, (ndepth, img_h // 4, img_w // 4), work[dom_key][1]))
             except Exception as e:  # the bench line must still come out
@@ -1059,11 +1131,12 @@ def main():
             "library_default_is": "MVS_ASYNC_WGRAD unset, no set_async_wgrad call: side-stream weight gradients, joined by MVSNet's tail node at the "
                                   "end of the backward pass (MVS_TAIL_JOIN=0: inside the regulariser node, rounds 3-5)",
             "grad_bucket_bytes": bucket.nbytes if bucket is not None else 0,
+            "full": full,
         }
         if ms_sustained is not None:
             res["ms_per_step_sustained"] = ms_sustained
             res["sustained_steps"] = args.sustained
-        if cfg["kind"] == "cvp_infer":
+        if full and cfg["kind"] == "cvp_infer":
             # the 2-D feature pyramid (jdacs-ms/models/network.py:16-41: nine 3x3 convolutions per image, at the three resolutions of
             # this config, N images): its algorithmic FLOPs, the time of its C-ABI calls (HIP events, one more pass of the K steps)
             # and its share of the step
@@ -1100,12 +1173,12 @@ def main():
                 res["step_host_fwd_bwd_rest_ms"] = [[round((phase_marks[2 * i] - host_marks[i]) * 1e3, 2),
                                                       round((phase_marks[2 * i + 1] - phase_marks[2 * i]) * 1e3, 2),
                                                       round((host_marks[i + 1] - phase_marks[2 * i + 1]) * 1e3, 2)] for i in range(args.steps)][:6]
-        if not args.no_cpu_baseline and world == 1 and args.config == 2:   # rank 0 at N=1 only (bench contract)
+        if full and not args.no_cpu_baseline and world == 1 and args.config == 2:   # rank 0 at N=1 only (bench contract)
             try:
                 res["cpu_baseline"] = cpu_baseline(state0, 1)
             except Exception as e:  # the bench line must still come out
                 res["cpu_baseline"] = {"value": None, "error": repr(e)}
-        want_ref = args.gpu_reference == 1 or (args.gpu_reference < 0 and world == 1 and args.config == 2 and not args.no_cpu_baseline)
+        want_ref = args.gpu_reference == 1 or (args.gpu_reference < 0 and full and world == 1 and args.config == 2 and not args.no_cpu_baseline)
         if want_ref and args.config == 2:
             try:
                 from oracle import ref_torch as R

@@ -25,18 +25,18 @@ case "$what" in
       echo "run $i: exit $rc: $(tail -1 $out/pytest_$i.log)" | tee -a $out/green.log
     done ;;
   ab)     # bash tools/gpu_r6.sh ab <dir> "<spec>;<spec>" [reps] [config]
-    timeout 1200 python bench.py --config ${5:-2} --steps 20 --warmup 5 $short --ab "$3" --ab-reps ${4:-6} > $out/bench_ab.json 2> $out/bench_ab.err; echo "bench exit $?"; summ $out/bench_ab.json ;;
+    timeout 1200 python bench.py --full --config ${5:-2} --steps 20 --warmup 5 $short --ab "$3" --ab-reps ${4:-6} > $out/bench_ab.json 2> $out/bench_ab.err; echo "bench exit $?"; summ $out/bench_ab.json ;;
   ktable) # uncontended per-call kernel table (synchronous weight gradients)
     MVS_ASYNC_WGRAD=0 timeout 600 python bench.py --config ${3:-2} --steps 10 --warmup 3 --time-all-kernels $short > $out/bench_k_sync.json 2> $out/bench_k_sync.err
     grep "ms/step" $out/bench_k_sync.err > $out/kernel_table_sync_mode.txt; head -${4:-70} $out/kernel_table_sync_mode.txt ;;
   line)   # short bench line of a config
-    timeout 900 python bench.py --config ${3:-2} --steps 20 --warmup 5 $short > $out/bench_c${3:-2}.json 2> $out/bench_c${3:-2}.err; echo "exit $?"; summ $out/bench_c${3:-2}.json ;;
+    timeout 900 python bench.py --full --config ${3:-2} --steps 20 --warmup 5 $short > $out/bench_c${3:-2}.json 2> $out/bench_c${3:-2}.err; echo "exit $?"; summ $out/bench_c${3:-2}.json ;;
   libab)  # bash tools/gpu_r6.sh libab <dir> [config] [reps]: two BUILDS of the library (tools/ab/lib_old.so, lib_new.so), alternating short bench lines
     lib=self-supervised-mvs_amd/libmvs_hip.so; cp $lib /tmp/lib_keep.so
     for i in $(seq 1 ${4:-3}); do
       for v in old new; do
         cp tools/ab/lib_$v.so $lib
-        timeout 600 python bench.py --config ${3:-2} --steps 20 --warmup 5 $short > $out/bench_${v}_$i.json 2> $out/bench_${v}_$i.err
+        timeout 600 python bench.py --full --config ${3:-2} --steps 20 --warmup 5 $short > $out/bench_${v}_$i.json 2> $out/bench_${v}_$i.err
         python - $out/bench_${v}_$i.json $v <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
