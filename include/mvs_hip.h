@@ -259,6 +259,29 @@ int mvs_unsup_loss_bwd(const float* ref, const float* const* views, const float*
                        const float* depth, int B, int V, int H, int W, float smooth_lambda, float* ws,
                        const float* grad_out, float* grad_depth, hipStream_t stream);
 
+/* ---- the same loss with its weights as arguments: jdacs-ms UnSupLoss at full resolution --------------------------------
+ * Serves jdacs-ms/losses/unsup_loss.py:18-82, which train.py calls once per pyramid level on the depth map nearest-up-sampled to
+ * the image size (jdacs-ms/train.py:222-229): total = w_reconstr reconstr + w_ssim ssim + w_smooth smooth (12 / 6 / 0.05
+ * there, smooth_lambda 1).  Layouts as above, but ref, views[v] are the FULL-resolution NHWC images [B,H,W,3] (one permute,
+ * no interpolation) and depth [B,H,W] is at image resolution; kinv / proj are built from the full-resolution intrinsics.
+ * The top-3 selection runs over the grid (one thread per pixel, per-workgroup partial rows with int32 selection counts, one
+ * workgroup finishing them in a fixed order) instead of in a single workgroup.  Same selection rule as mvs_unsup_loss_fwd:
+ * strict '<' insertion (ties go to the lower view index), entries >= 1e4 contribute nothing.
+ * Limits: 3 <= V <= 10, B >= 1, H >= 3, W >= 3, B*H*W <= 2^29 (32-bit pixel offsets); anything else is rejected before any
+ * launch with a negative code and a message naming the limit (the workspace query answers -1).
+ * Deterministic: no float atomics; every reduction is fixed-order, so two identical calls give bitwise-identical outputs and
+ * gradients.  ws: caller-owned scratch of mvs_unsup_loss_weighted_workspace_floats() floats, filled by the forward and read by
+ * the backward (same weights).  After the forward, ws[V*n*4 + (4V+2)*ceil(n/256) + 48 + v] (n = B*H*W) holds the number of
+ * pixels that selected view v as int32. */
+long long mvs_unsup_loss_weighted_workspace_floats(int B, int V, int H, int W);
+int mvs_unsup_loss_weighted_fwd(const float* ref, const float* const* views, const float* kinv, const float* proj,
+                                const float* depth, int B, int V, int H, int W, float w_reconstr, float w_ssim,
+                                float w_smooth, float smooth_lambda, float* ws, float* out, hipStream_t stream);
+int mvs_unsup_loss_weighted_bwd(const float* ref, const float* const* views, const float* kinv, const float* proj,
+                                const float* depth, int B, int V, int H, int W, float w_reconstr, float w_ssim,
+                                float w_smooth, float smooth_lambda, float* ws, const float* grad_out, float* grad_depth,
+                                hipStream_t stream);
+
 /* ---- stage glue of CVP-MVSNet --------------------------------------------------------------------
  * Replaces calDepthHypo (jdacs-ms/models/modules.py:107-206): hypos[b,k] = ref_depths[b] + (k - 4) * interval_b, k = 0..7,
  * interval_b = mean over the pixels of |depth change that moves the projection into source view 0 by one pixel along the

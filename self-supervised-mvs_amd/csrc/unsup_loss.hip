@@ -11,6 +11,11 @@
 // Layouts: images NHWC [B,H,W,3] at quarter resolution (the host does F.interpolate(0.25) + permute, no gradient),
 // depth [B,H,W], kinv [B,9] = K_ref^-1, proj [B,V,12] = K_ref.[R_rel|t_rel] (3x4, row major).
 // Only the depth map receives a gradient, like in the reference's training step (the images are inputs).
+//
+// The weighted entries (mvs_unsup_loss_weighted_*) serve jdacs-ms/losses/unsup_loss.py:18-82, which runs at full image
+// resolution (jdacs-ms/train.py:222-229) with weights 12 / 6 / 0.05 and lambda 1: the same warp / terms / backward kernels
+// with the weights as arguments, but the top-3 selection over the pixels is spread over the grid (unsup_rows_kernel ->
+// unsup_select_kernel -> unsup_select_finish_kernel) instead of walking every pixel in one workgroup.
 #include "mvs_rt.h"
 
 #define UNSUP_MAXV 10
@@ -29,7 +34,11 @@ struct UnsupArgs {
     float* coef;                      // ws: [2,B,H-2,W-2,3,3] SSIM derivative coefficients (bwd)
     float* out;                       // fwd: [4] total, reconstr, ssim, smooth
     float* gdepth;                    // bwd: [B,H,W]
+    float* rows;                      // weighted ws: [4V+2] row totals of part
+    float* selsum;                    // weighted ws: [nblk] per-workgroup sums of the selected values
+    int* selcnt;                      // weighted ws: [V][nblk] per-workgroup selection counts (exact)
     float lambda;
+    float w_rec, w_ssim, w_smooth;    // term weights of the total
     int B, V, H, W, nblk;
 };
 
@@ -192,6 +201,22 @@ __global__ __launch_bounds__(256) void unsup_terms_kernel(UnsupArgs a) {
     }
 }
 
+// the three smallest of r_v + 1e4 * (1 - mask_v) at pixel i (unsup_loss.py:72-81): strict '<' insertion, so ties go to the
+// lower view index; iv[k] = -1 where fewer than k + 1 views exist
+__device__ __forceinline__ void unsup_top3(const float* rv, const float* __restrict__ mask, size_t n, int i, int V,
+                                          float (&bv)[3], int (&iv)[3]) {
+    float b0 = 3.0e38f, b1 = 3.0e38f, b2 = 3.0e38f;
+    int i0 = -1, i1 = -1, i2 = -1;
+    for (int v = 0; v < V; ++v) {
+        const float val = rv[v] + 1e4f * (1.0f - mask[(size_t)v * n + i]);
+        if (val < b0) { b2 = b1; i2 = i1; b1 = b0; i1 = i0; b0 = val; i0 = v; }
+        else if (val < b1) { b2 = b1; i2 = i1; b1 = val; i1 = v; }
+        else if (val < b2) { b2 = val; i2 = v; }
+    }
+    bv[0] = b0; bv[1] = b1; bv[2] = b2;
+    iv[0] = i0; iv[1] = i1; iv[2] = i2;
+}
+
 // ---- forward 3: finish the sums, per-pixel top-3 over the views, total -------------------------------------------
 // saved[0..V) r_v (per-view reconstruction term), saved[16], saved[17] SSIM means of views 1/2, saved[18] smoothness,
 // saved[19] reconstruction loss, saved[20] total, saved[32..32+V) number of pixels that selected view v
@@ -227,16 +252,9 @@ __global__ __launch_bounds__(256) void unsup_finalize_kernel(UnsupArgs a) {
 #pragma unroll
     for (int k = 0; k <= UNSUP_MAXV; ++k) acc[k] = 0.f;
     for (int i = tid; i < n; i += 256) {
-        float b0 = 3.0e38f, b1 = 3.0e38f, b2 = 3.0e38f;
-        int i0 = -1, i1 = -1, i2 = -1;
-        for (int v = 0; v < a.V; ++v) {
-            const float val = rv[v] + 1e4f * (1.0f - a.mask[(size_t)v * n + i]);
-            if (val < b0) { b2 = b1; i2 = i1; b1 = b0; i1 = i0; b0 = val; i0 = v; }
-            else if (val < b1) { b2 = b1; i2 = i1; b1 = val; i1 = v; }
-            else if (val < b2) { b2 = val; i2 = v; }
-        }
-        const float bv[3] = {b0, b1, b2};
-        const int iv[3] = {i0, i1, i2};
+        float bv[3];
+        int iv[3];
+        unsup_top3(rv, a.mask, n, i, a.V, bv, iv);
 #pragma unroll
         for (int k = 0; k < 3; ++k)
             if (iv[k] >= 0 && bv[k] < 1e4f) {
@@ -249,11 +267,107 @@ __global__ __launch_bounds__(256) void unsup_finalize_kernel(UnsupArgs a) {
     if (tid == 0) {
         const float reconstr = acc[UNSUP_MAXV] / (float)n;
         const float ssim = a.saved[16] + (a.V > 1 ? a.saved[17] : 0.f);
-        const float total = 12.f * reconstr + 6.f * ssim + 0.18f * a.saved[18];
+        const float total = a.w_rec * reconstr + a.w_ssim * ssim + a.w_smooth * a.saved[18];
         a.saved[19] = reconstr;
         a.saved[20] = total;
         for (int v = 0; v < a.V; ++v) a.saved[32 + v] = acc[v];
         a.out[0] = total; a.out[1] = reconstr; a.out[2] = ssim; a.out[3] = a.saved[18];
+    }
+}
+
+// ---- forward 3 of the weighted entries, over the grid (the selection of unsup_finalize_kernel without its pixel walk) ----
+// per-view reconstruction term r_v from the row totals (unsup_finalize_kernel's formula, step 1)
+__device__ __forceinline__ float unsup_view_term(const float* __restrict__ rows, int v, const UnsupArgs& a) {
+    const int n = a.B * a.H * a.W;
+    const float photo = rows[4 * v] / ((float)n * 3.f);
+    const float gx = rows[4 * v + 1] / ((float)a.B * a.H * (a.W - 1) * 3.f);
+    const float gy = rows[4 * v + 2] / ((float)a.B * (a.H - 1) * a.W * 3.f);
+    return 0.5f * photo + 0.5f * (gx + gy);
+}
+
+// (a) one workgroup per partial row of unsup_terms_kernel: rows[r] = its total, summed in unsup_finalize_kernel's order
+__global__ __launch_bounds__(256) void unsup_rows_kernel(UnsupArgs a) {
+    __shared__ float red[4];
+    const int r = blockIdx.x;
+    float s[1] = {0.f};
+    for (int k = threadIdx.x; k < a.nblk; k += 256) s[0] += a.part[(size_t)r * a.nblk + k];
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) a.rows[r] = s[0];
+}
+
+// (b) one thread per pixel: top-3 selection; per workgroup the sum of the selected values and the per-view counts.  A
+// workgroup's count of one view is at most 256, exact in the fp32 tree sum; the rows are stored as int32.
+__global__ __launch_bounds__(256) void unsup_select_kernel(UnsupArgs a) {
+    __shared__ float red[4 * (UNSUP_MAXV + 1)];
+    __shared__ float rv[UNSUP_MAXV];
+    const int n = a.B * a.H * a.W;
+    const int tid = threadIdx.x, i = blockIdx.x * 256 + tid;
+    if (tid < a.V) rv[tid] = unsup_view_term(a.rows, tid, a);
+    __syncthreads();
+    float acc[UNSUP_MAXV + 1];
+#pragma unroll
+    for (int k = 0; k <= UNSUP_MAXV; ++k) acc[k] = 0.f;
+    if (i < n) {
+        float bv[3];
+        int iv[3];
+        unsup_top3(rv, a.mask, n, i, a.V, bv, iv);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (iv[k] >= 0 && bv[k] < 1e4f) {
+                acc[UNSUP_MAXV] += bv[k];
+#pragma unroll
+                for (int v = 0; v < UNSUP_MAXV; ++v) acc[v] += (iv[k] == v) ? 1.f : 0.f;
+            }
+    }
+    block_sum<UNSUP_MAXV + 1>(acc, red);
+    if (tid == 0) {
+        a.selsum[blockIdx.x] = acc[UNSUP_MAXV];
+#pragma unroll
+        for (int v = 0; v < UNSUP_MAXV; ++v)
+            if (v < a.V) a.selcnt[(size_t)v * a.nblk + blockIdx.x] = (int)acc[v];
+    }
+}
+
+// (c) one workgroup finishes the rows in a fixed order: out[4] and the saved[] slots unsup_finalize_kernel writes, plus
+// saved[48..48+V) = the exact selection counts as int32
+__global__ __launch_bounds__(256) void unsup_select_finish_kernel(UnsupArgs a) {
+    __shared__ float red[4];
+    __shared__ int cred[UNSUP_MAXV][256];
+    const int n = a.B * a.H * a.W;
+    const int tid = threadIdx.x;
+    float s[1] = {0.f};
+    int c[UNSUP_MAXV];
+#pragma unroll
+    for (int v = 0; v < UNSUP_MAXV; ++v) c[v] = 0;
+    for (int k = tid; k < a.nblk; k += 256) {
+        s[0] += a.selsum[k];
+#pragma unroll
+        for (int v = 0; v < UNSUP_MAXV; ++v)
+            if (v < a.V) c[v] += a.selcnt[(size_t)v * a.nblk + k];
+    }
+    block_sum<1>(s, red);
+#pragma unroll
+    for (int v = 0; v < UNSUP_MAXV; ++v) cred[v][tid] = c[v];
+    __syncthreads();
+    if (tid < a.V) {   // integer sums: exact in any order
+        int t = 0;
+        for (int k = 0; k < 256; ++k) t += cred[tid][k];
+        a.saved[tid] = unsup_view_term(a.rows, tid, a);
+        a.saved[32 + tid] = (float)t;
+        reinterpret_cast<int*>(a.saved)[48 + tid] = t;
+        if (tid < 2) a.saved[16 + tid] = a.rows[4 * tid + 3] / ((float)a.B * (a.H - 2) * (a.W - 2) * 3.f);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const float smooth = a.rows[4 * a.V] / ((float)a.B * a.H * (a.W - 1)) +
+                             a.rows[4 * a.V + 1] / ((float)a.B * (a.H - 1) * a.W);
+        const float reconstr = s[0] / (float)n;
+        const float ssim = a.saved[16] + a.saved[17];
+        const float total = a.w_rec * reconstr + a.w_ssim * ssim + a.w_smooth * smooth;
+        a.saved[18] = smooth;
+        a.saved[19] = reconstr;
+        a.saved[20] = total;
+        a.out[0] = total; a.out[1] = reconstr; a.out[2] = ssim; a.out[3] = smooth;
     }
 }
 
@@ -292,10 +406,10 @@ __global__ __launch_bounds__(256) void unsup_grad_depth_kernel(UnsupArgs a) {
     const float* __restrict__ rf = a.ref + (size_t)i * 3;
     const bool hx = px + 1 < a.W, hy = py + 1 < a.H, lx = px > 0, ly = py > 0;
     float gd = 0.f;
-    const float kssim = 6.f * g / ((float)a.B * (a.H - 2) * (a.W - 2) * 3.f);
+    const float kssim = a.w_ssim * g / ((float)a.B * (a.H - 2) * (a.W - 2) * 3.f);
     const int WH = a.H - 2, WW = a.W - 2;
     for (int v = 0; v < a.V; ++v) {
-        const float sel = 12.f * g * a.saved[32 + v] / (float)n;                       // d total / d r_v
+        const float sel = a.w_rec * g * a.saved[32 + v] / (float)n;                    // d total / d r_v
         const float kph = sel * 0.5f / ((float)n * 3.f);
         const float kgx = sel * 0.5f / ((float)a.B * a.H * (a.W - 1) * 3.f);
         const float kgy = sel * 0.5f / ((float)a.B * (a.H - 1) * a.W * 3.f);
@@ -345,7 +459,7 @@ __global__ __launch_bounds__(256) void unsup_grad_depth_kernel(UnsupArgs a) {
     }
     // smoothness (modules.py:66-77)
     {
-        const float ksx = 0.18f * g / ((float)a.B * a.H * (a.W - 1)), ksy = 0.18f * g / ((float)a.B * (a.H - 1) * a.W);
+        const float ksx = a.w_smooth * g / ((float)a.B * a.H * (a.W - 1)), ksy = a.w_smooth * g / ((float)a.B * (a.H - 1) * a.W);
         const float* __restrict__ d = a.depth + i;
         if (hx) {
             const float wgt = expf(-a.lambda * ((fabsf(rf[0] - rf[3]) + fabsf(rf[1] - rf[4]) + fabsf(rf[2] - rf[5])) / 3.0f));
@@ -380,6 +494,7 @@ static int unsup_fill(UnsupArgs& a, const float* ref, const float* const* views,
     MVS_REQUIRE(B > 0 && H >= 3 && W >= 3, MVS_ERR_SHAPE, "unsup_loss: bad shape B=%d H=%d W=%d", B, H, W);
     a = UnsupArgs{};
     a.ref = ref; a.kinv = kinv; a.proj = proj; a.depth = depth; a.lambda = lambda;
+    a.w_rec = 12.f; a.w_ssim = 6.f; a.w_smooth = 0.18f;   // jdacs/losses/unsup_loss.py:83
     for (int v = 0; v < V; ++v) {
         MVS_REQUIRE(views[v], MVS_ERR_NULL, "unsup_loss: null view image %d", v);
         a.view[v] = views[v];
@@ -430,4 +545,76 @@ extern "C" int mvs_unsup_loss_bwd(const float* ref, const float* const* views, c
     MVS_LAUNCH(unsup_ssim_coef_kernel, dim3((nw + 255) / 256, 2), dim3(256), 0, stream, a);
     MVS_LAUNCH(unsup_grad_depth_kernel, dim3(a.nblk), dim3(256), 0, stream, a);
     return mvs_check_launch("unsup_loss_bwd");
+}
+
+// ---- weighted entries (jdacs-ms/losses/unsup_loss.py:18-82 at full resolution) --------------------------------------
+// Limits: 3 <= V <= UNSUP_MAXV, H, W >= 3 and B*H*W <= UNSUP_MAX_PIXELS.  The kernels index pixels, pixel * 3 channel
+// offsets within one image, the grid's flat thread index and the per-view selection counts with 32-bit ints: all stay
+// below 3 * 2^29 + 255 < 2^31 at the largest admitted shape.  Everything that scales with V * n is addressed in size_t.
+#define UNSUP_MAX_PIXELS (1LL << 29)
+
+static int unsup_weighted_shape(int B, int V, int H, int W) {
+    MVS_REQUIRE(V >= 3 && V <= UNSUP_MAXV, MVS_ERR_UNSUPPORTED,
+                "unsup_loss_weighted: needs 3 <= V <= %d source views (top-3 selection, UNSUP_MAXV), got V=%d", UNSUP_MAXV, V);
+    MVS_REQUIRE(B >= 1, MVS_ERR_SHAPE, "unsup_loss_weighted: needs B >= 1, got B=%d", B);
+    MVS_REQUIRE(H >= 3 && W >= 3, MVS_ERR_SHAPE, "unsup_loss_weighted: needs H >= 3 and W >= 3 (3x3 SSIM window), got H=%d W=%d", H, W);
+    MVS_REQUIRE((long long)B * H * W <= UNSUP_MAX_PIXELS, MVS_ERR_SHAPE,
+                "unsup_loss_weighted: B*H*W = %lld exceeds UNSUP_MAX_PIXELS = %lld (32-bit pixel offsets)",
+                (long long)B * H * W, (long long)UNSUP_MAX_PIXELS);
+    return MVS_OK;
+}
+
+static int unsup_weighted_fill(UnsupArgs& a, const float* ref, const float* const* views, const float* kinv,
+                               const float* proj, const float* depth, int B, int V, int H, int W, float w_reconstr,
+                               float w_ssim, float w_smooth, float lambda, float* ws) {
+    int rc = unsup_weighted_shape(B, V, H, W);
+    if (rc) return rc;
+    rc = unsup_fill(a, ref, views, kinv, proj, depth, B, V, H, W, lambda, ws);
+    if (rc) return rc;
+    a.w_rec = w_reconstr; a.w_ssim = w_ssim; a.w_smooth = w_smooth;
+    a.rows = a.coef + 2LL * B * (H - 2) * (W - 2) * 9;
+    a.selsum = a.rows + 64;
+    a.selcnt = reinterpret_cast<int*>(a.selsum + a.nblk);
+    return MVS_OK;
+}
+
+// mvs_unsup_loss_workspace_floats() + 64 row totals + (V + 1) per-workgroup selection rows; -1 for a shape the entries reject
+extern "C" long long mvs_unsup_loss_weighted_workspace_floats(int B, int V, int H, int W) {
+    if (V < 3 || V > UNSUP_MAXV || B < 1 || H < 3 || W < 3 || (long long)B * H * W > UNSUP_MAX_PIXELS) return -1;
+    const long long n = (long long)B * H * W, nblk = (n + 255) / 256;
+    return mvs_unsup_loss_workspace_floats(B, V, H, W) + 64 + (V + 1LL) * nblk;
+}
+
+// out[4] = total = w_reconstr * reconstr + w_ssim * ssim + w_smooth * smooth, then the three terms (device memory)
+extern "C" int mvs_unsup_loss_weighted_fwd(const float* ref, const float* const* views, const float* kinv, const float* proj,
+                                           const float* depth, int B, int V, int H, int W, float w_reconstr, float w_ssim,
+                                           float w_smooth, float smooth_lambda, float* ws, float* out, hipStream_t stream) {
+    UnsupArgs a;
+    int rc = unsup_weighted_fill(a, ref, views, kinv, proj, depth, B, V, H, W, w_reconstr, w_ssim, w_smooth, smooth_lambda, ws);
+    if (rc) return rc;
+    MVS_REQUIRE(out, MVS_ERR_NULL, "unsup_loss_weighted_fwd: null output");
+    a.out = out;
+    MVS_LAUNCH(unsup_warp_kernel, dim3(a.nblk, V), dim3(256), 0, stream, a);
+    MVS_LAUNCH(unsup_terms_kernel, dim3(a.nblk, V + 1), dim3(256), 0, stream, a);
+    MVS_LAUNCH(unsup_rows_kernel, dim3(4 * V + 2), dim3(256), 0, stream, a);
+    MVS_LAUNCH(unsup_select_kernel, dim3(a.nblk), dim3(256), 0, stream, a);
+    MVS_LAUNCH(unsup_select_finish_kernel, dim3(1), dim3(256), 0, stream, a);
+    return mvs_check_launch("unsup_loss_weighted_fwd");
+}
+
+// ws: the workspace the weighted forward filled; grad_out: device scalar
+extern "C" int mvs_unsup_loss_weighted_bwd(const float* ref, const float* const* views, const float* kinv, const float* proj,
+                                           const float* depth, int B, int V, int H, int W, float w_reconstr, float w_ssim,
+                                           float w_smooth, float smooth_lambda, float* ws, const float* grad_out,
+                                           float* grad_depth, hipStream_t stream) {
+    UnsupArgs a;
+    int rc = unsup_weighted_fill(a, ref, views, kinv, proj, depth, B, V, H, W, w_reconstr, w_ssim, w_smooth, smooth_lambda, ws);
+    if (rc) return rc;
+    MVS_REQUIRE(grad_out && grad_depth, MVS_ERR_NULL, "unsup_loss_weighted_bwd: null gradient pointer");
+    a.gout = grad_out;
+    a.gdepth = grad_depth;
+    const int nw = B * (H - 2) * (W - 2);
+    MVS_LAUNCH(unsup_ssim_coef_kernel, dim3((nw + 255) / 256, 2), dim3(256), 0, stream, a);
+    MVS_LAUNCH(unsup_grad_depth_kernel, dim3(a.nblk), dim3(256), 0, stream, a);
+    return mvs_check_launch("unsup_loss_weighted_bwd");
 }

@@ -1886,6 +1886,58 @@ def unsup_loss(depth, ref_q, views_q, kinv, proj, smooth_lambda=1.0):
     return UnsupLossFn.apply(depth, ref_q, list(views_q), kinv, proj, smooth_lambda)
 
 
+class UnsupLossWeightedFn(torch.autograd.Function):
+    """The same loss with its term weights as arguments and the top-3 selection spread over the grid
+    (mvs_unsup_loss_weighted_fwd / _bwd): jdacs-ms/losses/unsup_loss.py:18-82 at full image resolution.  ref, views: NHWC
+    [B,H,W,3] at the depth map's resolution; depth [B,H,W] -> (total, reconstr, ssim, smooth), differentiable w.r.t. the depth
+    map only (the three terms are reported for logging)."""
+
+    @staticmethod
+    def forward(ctx, depth, ref, views, kinv, proj, weights, smooth_lambda):
+        lib = _lib_for(depth)
+        depth = depth.contiguous()
+        b, h, w = depth.shape
+        nv = len(views)
+        ref = ref.contiguous()
+        views = [v.contiguous() for v in views]
+        for t in [ref] + views:
+            if tuple(t.shape) != (b, h, w, 3):
+                raise ValueError("images must be NHWC [B,H,W,3] at the depth map's resolution = %s, got %s"
+                                 % ((b, h, w, 3), tuple(t.shape)))
+        if tuple(kinv.shape) != (b, 9) or tuple(proj.shape) != (b, nv, 12):
+            raise ValueError("kinv must be [B,9] and proj [B,V,12], got %s / %s" % (tuple(kinv.shape), tuple(proj.shape)))
+        kinv, proj = kinv.contiguous(), proj.contiguous()
+        nws = lib.raw("mvs_unsup_loss_weighted_workspace_floats", b, nv, h, w)
+        if nws < 0:
+            raise ValueError("unsup_loss_weighted: unsupported shape B=%d V=%d H=%d W=%d (3 <= V <= 10, H, W >= 3, B*H*W <= 2^29)"
+                             % (b, nv, h, w))
+        ws = torch.empty(nws, dtype=torch.float32, device=depth.device)
+        out = torch.empty(4, dtype=torch.float32, device=depth.device)
+        wts = tuple(float(x) for x in weights)
+        lib.call("mvs_unsup_loss_weighted_fwd", _p(ref), _ptr_array(views), _p(kinv), _p(proj), _p(depth), b, nv, h, w, *wts,
+                 float(smooth_lambda), _p(ws), _p(out), _stream(depth))
+        ctx.save_for_backward(depth, ref, kinv, proj, ws, *views)
+        ctx.cfg = wts + (float(smooth_lambda),)
+        total, reconstr, ssim, smooth = out[0], out[1], out[2], out[3]
+        ctx.mark_non_differentiable(reconstr, ssim, smooth)
+        return total, reconstr, ssim, smooth
+
+    @staticmethod
+    def backward(ctx, g_total, g_reconstr, g_ssim, g_smooth):
+        depth, ref, kinv, proj, ws, *views = ctx.saved_tensors
+        lib = _lib_for(depth)
+        b, h, w = depth.shape
+        g = g_total.contiguous().reshape(1).to(torch.float32)
+        gd = torch.empty_like(depth)
+        lib.call("mvs_unsup_loss_weighted_bwd", _p(ref), _ptr_array(views), _p(kinv), _p(proj), _p(depth), b, len(views), h, w,
+                 *ctx.cfg, _p(ws), _p(g), _p(gd), _stream(depth))
+        return gd, None, None, None, None, None, None
+
+
+def unsup_loss_weighted(depth, ref, views, kinv, proj, w_reconstr, w_ssim, w_smooth, smooth_lambda=1.0):
+    return UnsupLossWeightedFn.apply(depth, ref, list(views), kinv, proj, (w_reconstr, w_ssim, w_smooth), smooth_lambda)
+
+
 # ------------------------------------------------------------------------------------------------
 # SURVEY 8(f)-2: per-level depth hypotheses of CVP-MVSNet
 # ------------------------------------------------------------------------------------------------
