@@ -35,6 +35,12 @@ typedef struct ihipStream_t* hipStream_t; /* same opaque type as <hip/hip_runtim
 int mvs_version(void);              /* 100 == 0.1.0 */
 const char* mvs_last_error(void);   /* thread-local, valid until the next failing call */
 int mvs_is_emulation(void);         /* 0 in the product library */
+/* Launch trace (tests, diagnosis): every kernel launch the library checks notes a label naming the kernel and, where one label
+ * would cover several size-selected instantiations, which one ("conv_pers nw=8", "conv_igemm s1_small", "conv_wgrad_reduce wide").
+ * Writes the labels of this thread's launches since the previous call, comma-joined, into buf (cap bytes with the terminator;
+ * whole labels only; the first 64 are kept) and forgets them.  Returns the number of launches since the previous call.
+ * buf == NULL only clears.  Thread local, no allocation, no device work. */
+int mvs_launch_trace(char* buf, int cap);
 /* A/B knobs for measurements/tests (full-string keys; an unknown key is MVS_ERR_UNSUPPORTED): "sweep_fwd" 0 taps through
  * L1 | 1 LDS windows | 2,3 register-cached taps (default 3) | 6 quad-shared projection; "sweep_bwd" 0 per-wave windows |
  * 1 view pairs + LDS atomics; "fwd_dl" 0 | 1 per-plane depths staged in LDS (default) | 2 + in-block gather waits;

@@ -47,6 +47,7 @@ SIGNATURES = {
     "mvs_version": (_i, []),
     "mvs_last_error": (C.c_char_p, []),
     "mvs_is_emulation": (_i, []),
+    "mvs_launch_trace": (_i, [C.c_char_p, _i]),
     "mvs_set_tuning": (_i, [C.c_char_p, _i]),
     "mvs_get_tuning": (_i, [C.c_char_p, C.POINTER(_i)]),
     "mvs_plane_sweep_variance_fwd": (_i, [_f, C.POINTER(C.c_void_p), _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _s]),
@@ -158,6 +159,13 @@ class MvsLib:
 
     def raw(self, name: str, *args):
         return getattr(self, "_" + name)(*args)
+
+    def launch_trace(self):
+        """Labels of the kernel launches this thread has made through the library since the previous call (mvs_launch_trace):
+        which size-selected kernel a call actually took.  At most the first 64 are kept."""
+        buf = C.create_string_buffer(4096)
+        self._mvs_launch_trace(buf, len(buf))
+        return [s for s in buf.value.decode().split(",") if s]
 
 
 _INSTANCE = None

@@ -1526,6 +1526,14 @@ int run_conv_x3_fwd(const ConvArgs& a, const float* w, int wlayout, int flip, fl
 extern int g_conv_x3;
 int g_conv_xcd = 1;     // tuning knob "xcd": XCD-aware tile order in the broadcast-operand forward and the Cout == 8 weight gradient
 
+// launch-check labels (error messages, and the launch trace the tests read: mvs_launch_trace) say which size-selected arm ran
+template <int GEOM>
+static const char* igemm_label() {
+    return GEOM == GEOM_S1 ? "conv_igemm s1" : GEOM == GEOM_S2 ? "conv_igemm s2" : GEOM == GEOM_TR2 ? "conv_igemm tr2" :
+           GEOM == GEOM_S1_SMALL ? "conv_igemm s1_small" : GEOM == GEOM_S2_SMALL ? "conv_igemm s2_small" :
+           GEOM == GEOM_TR2_SMALL ? "conv_igemm tr2_small" : GEOM == GEOM_TR2_PW ? "conv_igemm tr2_pw" : "conv_igemm";
+}
+
 template <int GEOM, int CC>
 static int launch_igemm_nb(const ConvArgs& a, int NB, int nblocks, hipStream_t st) {
     dim3 grid(nblocks, a.nb_total / NB), block(256);
@@ -1539,7 +1547,7 @@ static int launch_igemm_nb(const ConvArgs& a, int NB, int nblocks, hipStream_t s
             case 4: MVS_LAUNCH((conv_igemm_kernel<GEOM, CC, 4, 1>), grid, block, 0, st, a); break;
             default: mvs_set_error("conv igemm: Cout tile count %d unsupported", NB); return MVS_ERR_UNSUPPORTED;
         }
-        return mvs_check_launch("conv_igemm");
+        return mvs_check_launch(igemm_label<GEOM>());
     }
     switch (NB) {
         case 1: MVS_LAUNCH((conv_igemm_kernel<GEOM, CC, 1, 0>), grid, block, 0, st, a); break;
@@ -1547,7 +1555,7 @@ static int launch_igemm_nb(const ConvArgs& a, int NB, int nblocks, hipStream_t s
         case 4: MVS_LAUNCH((conv_igemm_kernel<GEOM, CC, 4, 0>), grid, block, 0, st, a); break;
         default: mvs_set_error("conv igemm: Cout tile count %d unsupported", NB); return MVS_ERR_UNSUPPORTED;
     }
-    return mvs_check_launch("conv_igemm");
+    return mvs_check_launch(igemm_label<GEOM>());
 }
 
 // Which tiling the generic kernel runs with.  Small volumes (deep U-Net levels) have too few tiles to fill 256 CUs: first one
@@ -1611,7 +1619,9 @@ static int plan_for(int op, int B, int D, int H, int W, int Cin, int Cout, int s
                 p.geom = GEOM_S1; p.flip = 1; p.Di = D; p.Hi = H; p.Wi = W;
                 p.cin1 = Cout == 1;
             } else {
-                MVS_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, MVS_ERR_SHAPE, "%s stride 2: D,H,W must be even", what);
+                MVS_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, MVS_ERR_SHAPE,
+                            "%s stride 2: D,H,W must be even, got %d x %d x %d (the input gradient runs as a transposed convolution over the "
+                            "D/2 x H/2 x W/2 grid of the output gradient)", what, D, H, W);
                 p.geom = GEOM_TR2; p.flip = 0; p.Di = D / 2; p.Hi = H / 2; p.Wi = W / 2;
             }
             return MVS_OK;
@@ -1717,7 +1727,7 @@ static int run_igemm(const IgemmPlan& p, const float* in, const float* wsrc, flo
             MVS_LAUNCH(conv_cout1_h4_kernel, dim3(B * a.ntd * a.nth * a.ntw), dim3(256), 0, st, a, wsrc);
         } else if (cin == 8) MVS_LAUNCH((conv_cout1_kernel<8>), dim3(nblocks), dim3(256), 0, st, a, wsrc);
         else MVS_LAUNCH((conv_cout1_kernel<16>), dim3(nblocks), dim3(256), 0, st, a, wsrc);
-        return mvs_check_launch("conv_cout1");
+        return mvs_check_launch(cin == 8 ? (g_conv_cout1_h4 ? "conv_cout1 h4" : "conv_cout1 cin=8") : "conv_cout1 cin=16");
     }
     int NB, kgeom;
     a.nb_total = mvs_cdiv(cout, 16) == 3 ? 4 : mvs_cdiv(cout, 16);
@@ -1795,7 +1805,7 @@ static int run_cin1(const IgemmPlan& p, const float* gy, const float* w, float* 
     else if (C == 8) MVS_LAUNCH((conv_cin1_kernel<8, 1>), grid, dim3(256), 0, st, gy, (const float*)ws, gx, p.B, p.Di, p.Hi, p.Wi, ep.bn_raw, ep.bn_stats, ep.slots, ep.nslots);
     else if (vpt == 4) MVS_LAUNCH((conv_cin1_kernel<16, 4>), grid, dim3(256), 0, st, gy, (const float*)ws, gx, p.B, p.Di, p.Hi, p.Wi, ep.bn_raw, ep.bn_stats, ep.slots, ep.nslots);
     else MVS_LAUNCH((conv_cin1_kernel<16, 1>), grid, dim3(256), 0, st, gy, (const float*)ws, gx, p.B, p.Di, p.Hi, p.Wi, ep.bn_raw, ep.bn_stats, ep.slots, ep.nslots);
-    return mvs_check_launch("conv_cin1");
+    return mvs_check_launch(vpt == 4 ? "conv_cin1 vpt=4" : "conv_cin1 vpt=1");
 }
 
 static const int WGRAD_MAX_GROUPS = 768;
@@ -1876,14 +1886,14 @@ static int run_wgrad(int geom, const float* X, const float* Gt, float* gw, float
         dim3 grids(groups, CX / cc, mvs_cdiv(CG, nbw * 16));
         if (geom == GEOM_S1) { if (cc == 16) launch_wgrad<GEOM_S1_SMALL, 16>(a, nbw, grids, st); else launch_wgrad<GEOM_S1_SMALL, 8>(a, nbw, grids, st); }
         else { if (cc == 16) launch_wgrad<GEOM_S2_SMALL, 16>(a, nbw, grids, st); else launch_wgrad<GEOM_S2_SMALL, 8>(a, nbw, grids, st); }
-        int rcs = mvs_check_launch("conv_wgrad (small tiles)");
+        int rcs = mvs_check_launch(nbw == 1 ? "conv_wgrad (small tiles) nbw=1" : "conv_wgrad (small tiles) nbw=2");
         if (rcs) return rcs;
         return wgrad_finish(ws, groups, CX, CG, gw, st);
     }
     dim3 grid(groups, CX / cc, mvs_cdiv(CG, nbw * 16));
     if (geom == GEOM_S1) { if (cc == 16) launch_wgrad<GEOM_S1, 16>(a, nbw, grid, st); else launch_wgrad<GEOM_S1, 8>(a, nbw, grid, st); }
     else { if (cc == 16) launch_wgrad<GEOM_S2, 16>(a, nbw, grid, st); else launch_wgrad<GEOM_S2, 8>(a, nbw, grid, st); }
-    int rc = mvs_check_launch("conv_wgrad");
+    int rc = mvs_check_launch(nbw == 1 ? "conv_wgrad nbw=1" : "conv_wgrad nbw=2");
     if (rc) return rc;
     return wgrad_finish(ws, groups, CX, CG, gw, st);
 }
@@ -1898,7 +1908,7 @@ static int wgrad_finish(float* ws, int nparts, int CX, int CG, float* gw, hipStr
         MVS_LAUNCH(conv_wgrad_reduce_wide_kernel, dim3(mvs_cdiv(n, 16)), dim3(256), 0, st, (const float*)ws, nparts, CX, CG, gw);
     else
         MVS_LAUNCH(conv_wgrad_reduce_kernel, dim3(mvs_cdiv(n, 256)), dim3(256), 0, st, (const float*)ws, nparts, CX, CG, gw);
-    return mvs_check_launch("conv_wgrad_reduce");
+    return mvs_check_launch(nparts > 32 ? "conv_wgrad_reduce wide" : "conv_wgrad_reduce narrow");
 }
 
 // ---- C ABI ---------------------------------------------------------------------------------------

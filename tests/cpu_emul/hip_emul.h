@@ -206,6 +206,11 @@ static inline float atomicAdd(float* addr, float v) {
 namespace emul {
 template <class F>
 void launch(dim3 grid, dim3 block, F body) {
+    // MVS_EMUL_DRY_LAUNCH=1: host code only -- argument checks, dispatch and the launch trace run, the kernel bodies do not
+    // (tests/test_conv_arm_dispatch.py walks shapes that would take the thread-per-lane emulation minutes)
+    if (const char* dry = getenv("MVS_EMUL_DRY_LAUNCH")) {
+        if (dry[0] == '1') return;
+    }
     const int nthreads = (int)(block.x * block.y * block.z);
     const int nwaves = (nthreads + 63) / 64;
     Block blk;

@@ -31,6 +31,24 @@ def test_header_symbols_exported_and_bound():
     assert lib.raw("mvs_is_emulation") == 0
 
 
+def test_launch_trace_entry_point():
+    """mvs_launch_trace on the product library without a GPU: declared, exported, bound; a call the host rejects launches nothing
+    and leaves no label; a NULL buffer only clears.  (What it reports after launches: tests/test_conv_arm_dispatch.py on the
+    emulation build, tests/test_gpu_conv_arms.py on the GPU.)"""
+    import ctypes as C
+    from mvs_amd import _lib
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    assert "mvs_launch_trace" in _declared() and "mvs_launch_trace" in _lib.SIGNATURES
+    lib = _lib.MvsLib()
+    lib.raw("mvs_launch_trace", None, 0)
+    with pytest.raises(ValueError, match="must be even, got 5 x 8 x 10"):
+        lib.call("mvs_conv3d_dgrad", None, None, None, None, None, 2, 5, 8, 10, 16, 32, 2, None, None, None, 0, 0, None)
+    buf = C.create_string_buffer(b"x" * 63, 64)
+    assert lib.raw("mvs_launch_trace", buf, 64) == 0 and buf.value == b""
+    assert lib.launch_trace() == []
+
+
 def test_product_fails_loudly_without_library(tmp_path):
     from mvs_amd import _lib
     with pytest.raises(RuntimeError, match="no CPU / PyTorch fallback"):

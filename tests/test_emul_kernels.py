@@ -13,6 +13,7 @@ import torch.nn.functional as F
 from conftest import (assert_as_accurate_as_fp32_reference, assert_grads_as_accurate_as_fp32_reference, load_golden, rel_l1,
                       state_dict_from)
 from emul_util import emul_lib  # noqa: F401
+import softargmin_cases
 from oracle import ref_torch as R
 
 torch.set_num_threads(4)
@@ -459,6 +460,19 @@ def test_softargmin_smallest_shapes(emul_lib, d, hw, per_pixel):
     e.backward(gd)
     assert float((dep - e).abs().max()) < 1e-3 and float((conf - ec).abs().max()) < 1e-5
     assert float((got - lg.grad).abs().max()) < 1e-4 * max(1.0, float(lg.grad.abs().max()))
+
+
+@pytest.mark.parametrize("d,hw,per_pixel,seed", softargmin_cases.CASES, ids=softargmin_cases.IDS)
+def test_softargmin_depth_count_switches(emul_lib, d, hw, per_pixel, seed):
+    """D either side of the kernel's two switches (32: four lane groups; 256: the logits no longer fit a lane's registers), lane
+    groups with unequal work, H * W not a multiple of 16, against the float64 oracle; the same cases run on the GPU
+    (test_gpu_parity.py).  Also checks here, without a GPU, that the seeds keep every E[d] away from an integer."""
+    from mvs_amd import ops
+    lg, hyp, gd = softargmin_cases.inputs(d, hw, per_pixel, seed)
+    lgg = lg.clone().requires_grad_(True)
+    dep, conf = ops.softargmin_conf(lgg, hyp)
+    dep.backward(gd)
+    softargmin_cases.check(dep.detach(), conf, lgg.grad, lg, hyp, gd)
 
 
 @pytest.mark.parametrize("cin,cout,stride,transposed,dims", [(8, 8, 1, False, (1, 1, 1)), (32, 8, 1, False, (1, 2, 3)),
@@ -1663,17 +1677,25 @@ def test_conv3d_persistent_lds_dma_kernel_equals_one_tile_kernel(emul_lib, cin, 
         gx = ops.conv3d_dgrad(gy, w, tuple(x.shape), stride, transposed, add=add, bn=(raw, stats, slots))
         return gx, slots
 
+    # the transposed geometry (conv11 forward, conv1's input gradient) reaches the persistent kernel only on full-size tiles: at these
+    # sizes the auto tiling would pick GEOM_TR2_SMALL first and BOTH runs would take the one-tile kernel (the launch trace says so)
+    tr2 = (stride == 2) and (transposed == (op == "fwd"))
     emul_lib.call("mvs_set_tuning", b"conv_pers", 0)
+    emul_lib.call("mvs_set_tuning", b"conv_small", 0 if tr2 else 1)
     try:
         ref, ref_slots = run()
         emul_lib.call("mvs_set_tuning", b"conv_pers", 1)
         emul_lib.call("mvs_set_tuning", b"conv_pers_min", 0)
         emul_lib.call("mvs_set_tuning", b"conv_pers_groups", groups)
+        emul_lib.launch_trace()
         got, got_slots = run()
+        trace = emul_lib.launch_trace()
     finally:
         emul_lib.call("mvs_set_tuning", b"conv_pers", 1)
         emul_lib.call("mvs_set_tuning", b"conv_pers_min", 1024)
         emul_lib.call("mvs_set_tuning", b"conv_pers_groups", 0)
+        emul_lib.call("mvs_set_tuning", b"conv_small", 1)
+    assert trace == ["conv_pack_weights", "conv_pers nw=8"], trace
     assert torch.equal(got, ref), float((got - ref).abs().max())
     s_ref, s_got = ref_slots.sum(-3), got_slots.sum(-3)
     assert torch.allclose(s_got, s_ref, rtol=1e-5, atol=1e-4)
@@ -1703,7 +1725,9 @@ def test_conv3d_persistent_weight_gradient(emul_lib, cin, cout, stride, transpos
         emul_lib.call("mvs_set_tuning", b"wgrad_pers", 1)
         emul_lib.call("mvs_set_tuning", b"conv_pers_min", 0)
         emul_lib.call("mvs_set_tuning", b"conv_pers_groups", groups)
+        emul_lib.launch_trace()
         new = ops.conv3d_wgrad(x, gy, wshape, stride, transposed)
+        assert emul_lib.launch_trace() == ["conv_wgrad_pers", "conv_wgrad_reduce narrow"]
     finally:
         emul_lib.call("mvs_set_tuning", b"wgrad_pers", 1)
         emul_lib.call("mvs_set_tuning", b"conv_pers_min", 1024)

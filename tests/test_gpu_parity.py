@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 from conftest import (assert_as_accurate_as_fp32_reference, assert_grads_as_accurate_as_fp32_reference, calibrate_batchnorm, load_golden,
                       rel_l1, state_dict_from)
+import softargmin_cases
 from oracle import ref_torch as R
 
 pytestmark = pytest.mark.gpu
@@ -253,6 +254,20 @@ def test_softargmin_smallest_shapes(dev, d, hw, per_pixel):
     assert float((lgg.grad.cpu() - lgc.grad).abs().max()) < 1e-4 * max(1.0, float(lgc.grad.abs().max()))
 
 
+@pytest.mark.parametrize("d,hw,per_pixel,seed", softargmin_cases.CASES, ids=softargmin_cases.IDS)
+def test_softargmin_depth_count_switches(dev, d, hw, per_pixel, seed):
+    """The kernel's size switch on hardware: D = 32 / 33 / 131 / 256 (four lane groups, logits in registers; 33 and 131 leave the
+    groups unequal work), D = 257 / 300 (four lane groups re-reading memory), fixed and per-pixel hypotheses, H * W not a multiple
+    of a wave's 16 pixels; forward and backward against oracle.ref_torch.softargmin_conf in float64.  No pixel is masked: the
+    seeds keep every pixel's E[d] more than 1e-3 from an integer (asserted in softargmin_cases.check)."""
+    from mvs_amd import ops
+    lg, hyp, gd = softargmin_cases.inputs(d, hw, per_pixel, seed)
+    lgg = lg.to(dev).requires_grad_(True)
+    dep, conf = ops.softargmin_conf(lgg, hyp.to(dev))
+    dep.backward(gd.to(dev))
+    softargmin_cases.check(dep.detach().cpu(), conf.cpu(), lgg.grad.cpu(), lg, hyp, gd)
+
+
 @pytest.mark.parametrize("cin,cout,stride,transposed,dims", [(8, 8, 1, False, (1, 1, 1)), (32, 8, 1, False, (1, 2, 3)),
                                                              (8, 16, 2, False, (2, 2, 2)), (16, 8, 2, True, (1, 1, 1)),
                                                              (16, 16, 1, False, (1, 1, 17)), (8, 1, 1, False, (1, 1, 2)),
@@ -431,6 +446,9 @@ def test_conv3d_family_vs_torch(dev, conv_tiles, cin, cout, stride, transposed, 
     assert torch.allclose(s[1], (yr.detach() ** 2).sum(dim=(0, 2, 3, 4)), atol=5e-2, rtol=1e-4)
     gy = torch.randn(yr.shape, generator=g)
     yr.backward(gy)
+    # (the input gradient of a stride-2 convolution is served for even input dims only -- it runs as a transposed convolution that
+    #  writes 2 x the output gradient's grid -- and the host rejects odd ones by name: test_gpu_conv_arms.py /
+    #  test_conv_arm_dispatch.py::test_conv3d_stride2_input_gradient_rejects_odd_dims)
     if not (stride == 2 and not transposed and any(s % 2 for s in dims)):
         gx = ops.conv3d_dgrad(gy.to(dev), w.to(dev), tuple(x.shape), stride, transposed)
         assert float((gx.cpu() - xr.grad).abs().max()) < 5e-4
