@@ -265,6 +265,45 @@ int mvs_unsup_loss_bwd(const float* ref, const float* const* views, const float*
                        const float* depth, int B, int V, int H, int W, float smooth_lambda, float* ws,
                        const float* grad_out, float* grad_depth, hipStream_t stream);
 
+/* ---- JDACS co-segmentation, part 1: non-negative matrix factorisation V ~ W H (csrc/seg_loss_kernels.h) -------------------
+ * Replaces NMF / multiplicative_update_step / approximation_error (jdacs/models/seg_dff.py:21-106) as SegDFF.forward calls
+ * them (:128): P independent problems (one per batch item) in one call, no host synchronisation.
+ * V [P,n,m] fp32, non-negative.  W [P,n,k], H [P,k,m]: the initial factors on entry (the caller draws them: |randn| *
+ * sqrt(mean(V) / k), W before H; the kernels draw nothing), the result on exit.  update_h = 0: H stays as given and only W is
+ * updated (the reference's path for a caller-supplied H, :72-80).
+ * Per iteration, in the reference's order: VH = V H^t, HH = H H^t, WHH = W HH, entries == 0 become 1e-7, W *= VH / WHH; then with
+ * the NEW W: WV = W^t V, WWH = (W^t W) H, zeros become 1e-7, H *= WV / WWH.  Stopping rule (:91-102): e0 = |V - W H|_F before the
+ * first iteration; after iterations 0, 10, 20, ... e = |V - W H|_F, stop when (e_prev - e) / e0 < tol, else e_prev = e.  tol <= 0
+ * disables the test (then only e0 is evaluated).  The decision is taken on the device; launches enqueued after it return at once.
+ * status [P,4] (device floats): iterations run, number of non-finite entries of the returned W (exact below 2^24), e0, the last e
+ * evaluated.  ws: mvs_nmf_workspace_floats() floats (second W buffer, per-workgroup partial rows, the solve state).
+ * Limits: 1 <= P <= 65535, 1 <= k <= 8, n >= k, m >= k, n*m < 2^31, 1 <= max_iter <= 100000; no alignment demand on n or m.  The
+ * workspace query answers -1 for a shape the solve rejects.  Deterministic: every cross-workgroup sum is partial rows + a
+ * fixed-order finish.  2 launches per iteration + 2 (+ 2 when the reference tests after the last iteration). */
+long long mvs_nmf_workspace_floats(int P, int n, int m, int k);
+int mvs_nmf_solve(const float* V, float* W, float* H, int P, int n, int m, int k, int update_h, int max_iter, float tol,
+                  float* ws, float* status, hipStream_t stream);
+
+/* ---- JDACS co-segmentation, part 2: the segmentation loss (csrc/seg_loss_kernels.h) ------------------------------------------
+ * Replaces compute_seg_loss (jdacs/losses/unsup_seg_loss.py:21-34) for every source view of UnSupSegLoss.forward (:62-75),
+ * with its inverse_warping (jdacs/losses/homography.py:186-351).  ref_seg [B,H,W,K] and view_segs (HOST array of V device
+ * pointers [B,H,W,K]) are the segmentation maps already at the depth map's resolution; kinv [B,9], proj [B,V,12], depth [B,H,W]
+ * as for mvs_unsup_loss_fwd.  Per source view: logits = the K bilinearly warped values (sample geometry and validity mask of
+ * mvs_unsup_loss_fwd), target = index of the FIRST maximum of ref_seg at the pixel, term = mean over all batch items' pixels with
+ * mask > 0.5 of logsumexp(logits) - logits[target].  out [1+V] (device): the sum over the views, then every view's term.  A view
+ * without a valid pixel gives 0 / 0 = NaN (and so does the sum), as F.cross_entropy on an empty selection does.
+ * Backward: only the depth map receives a gradient, through the sample coordinates, with the reference's clamped-index weights;
+ * the maps and the mask carry none (seg_dff.py:142).  ws: mvs_seg_loss_workspace_floats() floats, filled by the forward and read
+ * by the backward; grad_out: device scalar (gradient of out[0]).
+ * Limits: 1 <= V <= 10 (no top-3 selection here, N = 2 works), 2 <= K <= 8, B >= 1, H, W >= 2, B*H*W*K < 2^31.  The workspace
+ * query answers -1 otherwise.  Two launches forward, one backward; deterministic reductions. */
+long long mvs_seg_loss_workspace_floats(int B, int V, int H, int W, int K);
+int mvs_seg_loss_fwd(const float* ref_seg, const float* const* view_segs, const float* kinv, const float* proj,
+                     const float* depth, int B, int V, int H, int W, int K, float* ws, float* out, hipStream_t stream);
+int mvs_seg_loss_bwd(const float* ref_seg, const float* const* view_segs, const float* kinv, const float* proj,
+                     const float* depth, int B, int V, int H, int W, int K, float* ws, const float* grad_out,
+                     float* grad_depth, hipStream_t stream);
+
 /* ---- the same loss with its weights as arguments: jdacs-ms UnSupLoss at full resolution --------------------------------
  * Serves jdacs-ms/losses/unsup_loss.py:18-82, which train.py calls once per pyramid level on the depth map nearest-up-sampled to
  * the image size (jdacs-ms/train.py:222-229): total = w_reconstr reconstr + w_ssim ssim + w_smooth smooth (12 / 6 / 0.05

@@ -105,6 +105,11 @@ SIGNATURES = {
     "mvs_unsup_loss_weighted_fwd": (_i, [_f, C.POINTER(C.c_void_p), _f, _f, _f, _i, _i, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _s]),
     "mvs_unsup_loss_weighted_bwd": (_i, [_f, C.POINTER(C.c_void_p), _f, _f, _f, _i, _i, _i, _i, _fl, _fl, _fl, _fl, _f, _f, _f,
                                          _s]),
+    "mvs_nmf_workspace_floats": (_ll, [_i, _i, _i, _i]),
+    "mvs_nmf_solve": (_i, [_f, _f, _f, _i, _i, _i, _i, _i, _i, _fl, _f, _f, _s]),
+    "mvs_seg_loss_workspace_floats": (_ll, [_i, _i, _i, _i, _i]),
+    "mvs_seg_loss_fwd": (_i, [_f, C.POINTER(C.c_void_p), _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _s]),
+    "mvs_seg_loss_bwd": (_i, [_f, C.POINTER(C.c_void_p), _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _s]),
 }
 
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_CONVT_FWD, OP_CONVT_DGRAD, OP_CONVT_WGRAD = range(6)

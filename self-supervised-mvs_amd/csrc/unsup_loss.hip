@@ -49,13 +49,13 @@ __device__ __forceinline__ float sgn(float z) { return z > 0.f ? 1.f : (z < 0.f 
 // sample geometry of one (pixel, view): everything the forward and the backward need
 struct UnsupSample {
     float fx, fy;        // x1c - x, y1c - y (weights formed with the CLAMPED upper indices, homography.py:328-331)
-    int ia, ib, ic, id;  // element offsets of the taps a=(y0,x0) b=(y1,x0) c=(y0,x1) d=(y1,x1) within one image
+    int ia, ib, ic, id;  // element offsets of the taps a=(y0,x0) b=(y1,x0) c=(y0,x1) d=(y1,x1) within one image of C channels
     float valid;
     float dxdd, dydd;    // d x / d depth, d y / d depth
 };
 
 __device__ __forceinline__ UnsupSample unsup_sample(const float* __restrict__ kinv, const float* __restrict__ P,
-                                                     float depth, int px, int py, int H, int W) {
+                                                     float depth, int px, int py, int H, int W, int C = 3) {
     UnsupSample s;
     const float u = (float)px, v = (float)py;
     // ray = K^-1 (u, v, 1); cam = ray * depth (homography.py:245-247)
@@ -80,7 +80,7 @@ __device__ __forceinline__ UnsupSample unsup_sample(const float* __restrict__ ki
     const int ix0 = finite ? (int)x0c : 0, ix1 = finite ? (int)x1c : 0, iy0 = finite ? (int)y0c : 0, iy1 = finite ? (int)y1c : 0;
     s.fx = x1c - x;
     s.fy = y1c - y;
-    s.ia = (iy0 * W + ix0) * 3; s.ib = (iy1 * W + ix0) * 3; s.ic = (iy0 * W + ix1) * 3; s.id = (iy1 * W + ix1) * 3;
+    s.ia = (iy0 * W + ix0) * C; s.ib = (iy1 * W + ix0) * C; s.ic = (iy0 * W + ix1) * C; s.id = (iy1 * W + ix1) * C;
     // d(X/Z)/d depth with dX/dd = P[0..2].ray etc.
     const float dX = fmaf(P[0], r0, fmaf(P[1], r1, P[2] * r2));
     const float dY = fmaf(P[4], r0, fmaf(P[5], r1, P[6] * r2));
@@ -618,3 +618,6 @@ extern "C" int mvs_unsup_loss_weighted_bwd(const float* ref, const float* const*
     MVS_LAUNCH(unsup_grad_depth_kernel, dim3(a.nblk), dim3(256), 0, stream, a);
     return mvs_check_launch("unsup_loss_weighted_bwd");
 }
+
+// ---- the co-segmentation loss of JDACS (NMF solve + UnSupSegLoss): same translation unit, it shares unsup_sample ----
+#include "seg_loss_kernels.h"

@@ -1939,6 +1939,93 @@ def unsup_loss_weighted(depth, ref, views, kinv, proj, w_reconstr, w_ssim, w_smo
 
 
 # ------------------------------------------------------------------------------------------------
+# JDACS co-segmentation: NMF solve + segmentation loss (csrc/seg_loss_kernels.h)
+# ------------------------------------------------------------------------------------------------
+def nmf_solve(V, W0, H0, update_h=True, max_iter=50, tol=1e-4):
+    """V [P,n,m] (or [n,m]) ~ W H by the multiplicative updates of jdacs/models/seg_dff.py:26-106, all P problems in one
+    mvs_nmf_solve call and without a host synchronisation.  W0 [P,n,k], H0 [P,k,m]: the initial factors (not modified).
+    Returns (W, H, status [P,4]): status rows = iterations run, non-finite entries of W, e0, last e (device tensor; reading
+    it is the caller's one synchronisation).  No autograd: the factors are constants of the training step."""
+    lib = _lib_for(V)
+    single = V.dim() == 2
+    if single:
+        V, W0, H0 = V.unsqueeze(0), W0.unsqueeze(0), H0.unsqueeze(0)
+    if V.dim() != 3 or W0.dim() != 3 or H0.dim() != 3:
+        raise ValueError("nmf_solve: V [P,n,m], W0 [P,n,k], H0 [P,k,m] expected, got %s %s %s"
+                         % (tuple(V.shape), tuple(W0.shape), tuple(H0.shape)))
+    P, n, m = V.shape
+    k = W0.shape[2]
+    if tuple(W0.shape) != (P, n, k) or tuple(H0.shape) != (P, k, m):
+        raise ValueError("nmf_solve: W0 must be [P,n,k] = %s and H0 [P,k,m] = %s, got %s / %s"
+                         % ((P, n, k), (P, k, m), tuple(W0.shape), tuple(H0.shape)))
+    _lib_for(W0), _lib_for(H0)
+    V = V.detach().contiguous()
+    W = W0.detach().clone(memory_format=torch.contiguous_format)
+    H = H0.detach().clone(memory_format=torch.contiguous_format)
+    nws = lib.raw("mvs_nmf_workspace_floats", P, n, m, k)
+    if nws < 0:
+        raise ValueError("nmf_solve: unsupported shape P=%d n=%d m=%d k=%d (1 <= k <= 8, n >= k, m >= k, n*m < 2^31)" % (P, n, m, k))
+    ws = torch.empty(nws, dtype=torch.float32, device=V.device)
+    status = torch.empty(P, 4, dtype=torch.float32, device=V.device)
+    lib.call("mvs_nmf_solve", _p(V), _p(W), _p(H), P, n, m, k, 1 if update_h else 0, int(max_iter), float(tol), _p(ws),
+             _p(status), _stream(V))
+    if single:
+        return W[0], H[0], status
+    return W, H, status
+
+
+class SegLossFn(torch.autograd.Function):
+    """depth [B,H,W] -> (total, per_view [V]): UnSupSegLoss.forward's warp + cross-entropy per source view
+    (jdacs/losses/unsup_seg_loss.py:62-75); differentiable w.r.t. the depth map only (the segmentation maps are constants,
+    jdacs/models/seg_dff.py:142)."""
+
+    @staticmethod
+    def forward(ctx, depth, ref_seg, view_segs, kinv, proj):
+        lib = _lib_for(depth)
+        depth = depth.contiguous()
+        b, h, w = depth.shape
+        nv = len(view_segs)
+        ref_seg = ref_seg.contiguous()
+        view_segs = [v.contiguous() for v in view_segs]
+        k = ref_seg.shape[-1]
+        for t in [ref_seg] + view_segs:
+            _lib_for(t)
+            if tuple(t.shape) != (b, h, w, k):
+                raise ValueError("segmentation maps must be [B,H,W,K] at the depth map's resolution = %s, got %s"
+                                 % ((b, h, w, k), tuple(t.shape)))
+        if tuple(kinv.shape) != (b, 9) or tuple(proj.shape) != (b, nv, 12):
+            raise ValueError("kinv must be [B,9] and proj [B,V,12], got %s / %s" % (tuple(kinv.shape), tuple(proj.shape)))
+        kinv, proj = kinv.contiguous(), proj.contiguous()
+        nws = lib.raw("mvs_seg_loss_workspace_floats", b, nv, h, w, k)
+        if nws < 0:
+            raise ValueError("seg_loss: unsupported shape B=%d V=%d H=%d W=%d K=%d (1 <= V <= 10, 2 <= K <= 8, H, W >= 2, "
+                             "B*H*W*K < 2^31)" % (b, nv, h, w, k))
+        ws = torch.empty(nws, dtype=torch.float32, device=depth.device)
+        out = torch.empty(1 + nv, dtype=torch.float32, device=depth.device)
+        lib.call("mvs_seg_loss_fwd", _p(ref_seg), _ptr_array(view_segs), _p(kinv), _p(proj), _p(depth), b, nv, h, w, k, _p(ws),
+                 _p(out), _stream(depth))
+        ctx.save_for_backward(depth, ref_seg, kinv, proj, ws, *view_segs)
+        total, per_view = out[0], out[1:]
+        ctx.mark_non_differentiable(per_view)   # reported for logging; the total is their sum
+        return total, per_view
+
+    @staticmethod
+    def backward(ctx, g_total, g_per_view):
+        depth, ref_seg, kinv, proj, ws, *view_segs = ctx.saved_tensors
+        lib = _lib_for(depth)
+        b, h, w = depth.shape
+        g = g_total.contiguous().reshape(1).to(torch.float32)
+        gd = torch.empty_like(depth)
+        lib.call("mvs_seg_loss_bwd", _p(ref_seg), _ptr_array(view_segs), _p(kinv), _p(proj), _p(depth), b, len(view_segs), h, w,
+                 ref_seg.shape[-1], _p(ws), _p(g), _p(gd), _stream(depth))
+        return gd, None, None, None, None
+
+
+def seg_loss(depth, ref_seg, view_segs, kinv, proj):
+    return SegLossFn.apply(depth, ref_seg, list(view_segs), kinv, proj)
+
+
+# ------------------------------------------------------------------------------------------------
 # SURVEY 8(f)-2: per-level depth hypotheses of CVP-MVSNet
 # ------------------------------------------------------------------------------------------------
 def depth_hypotheses(ref_depths: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
