@@ -8,8 +8,10 @@
  * Conventions
  *  - All pointers are DEVICE pointers owned by the caller (e.g. PyTorch's caching allocator); the
  *    library never allocates, frees or retains them.  Outputs are fully overwritten unless stated.
- *  - Work is enqueued on `stream` only; no call synchronises the device.  Re-entrant: no global
- *    mutable state (the last-error string is thread local).
+ *  - Work is enqueued on `stream` only; no call synchronises the device.  Re-entrant: the last-error
+ *    string and the launch trace are thread local.  The one piece of process-wide mutable state is
+ *    the tuning knobs (mvs_set_tuning): the launchers read them unsynchronised, so change them only
+ *    while no other thread is inside the library.
  *  - fp32 everywhere.  Feature maps are channels-last [B,H,W,C]; volumes channels-last [B,D,H,W,C]
  *    (== torch.channels_last / torch.channels_last_3d memory formats of NCHW / NCDHW tensors).
  *  - Return value: 0 on success, negative on error (MVS_ERR_*), message via mvs_last_error().
@@ -41,17 +43,10 @@ int mvs_is_emulation(void);         /* 0 in the product library */
  * whole labels only; the first 64 are kept) and forgets them.  Returns the number of launches since the previous call.
  * buf == NULL only clears.  Thread local, no allocation, no device work. */
 int mvs_launch_trace(char* buf, int cap);
-/* A/B knobs for measurements/tests (full-string keys; an unknown key is MVS_ERR_UNSUPPORTED): "sweep_fwd" 0 taps through
- * L1 | 1 LDS windows | 2,3 register-cached taps (default 3) | 6 quad-shared projection; "sweep_bwd" 0 per-wave windows |
- * 1 view pairs + LDS atomics; "fwd_dl" 0 | 1 per-plane depths staged in LDS (default) | 2 + in-block gather waits;
- * "bwd_gd" 2 (default: 2-plane gradient groups, 2 waves/SIMD) | 0 (1-plane groups, 3 waves/SIMD), "bwd_pf" 0 | 1 block
- * lookahead (1-2 views) | 2 one wave/SIMD (3-4 views), "bwd_dslab", "bwd_nowin", "bwd_cpt" (ignored); "nt", "tile_w", "dslab";
- * "conv_split", "conv_small", "conv_small_wgs", "tr2pw", "k8", "fs", "xcd"; "conv2d_s2_mfma", "wgrad2d_groups";
- * round 5: "conv_pers" / "conv_pers_min" / "conv_pers_groups" / "conv_pers_nw" (persistent LDS-DMA convolutions), "wgrad_pers",
- * "wgrad8_gs" 0 | 1 | 2 (conv0's weight gradient: 4x4x1-MFMA kernel | output-gradient-shifted form with eight | sixteen waves),
- * "wgrad8_groups" (its workgroups: 192 of 256 CUs on the side stream), "wgrad_groups".  The full table with ranges is in
- * csrc/plane_sweep.hip (mvs_set_tuning); the defaults are mirrored in _lib.DEFAULT_TUNING and checked by
- * tests/test_capi_symbols.py.  Process-wide, not part of the data path's contract. */
+/* Measurement knobs: integers that choose between kernels where the library has more than one (A/B runs, tests of the
+ * size-selected variants).  Full-string keys; an unknown key is MVS_ERR_UNSUPPORTED; a value outside the knob's range is clamped.
+ * The authoritative list with ranges, defaults and meanings is csrc/tuning.h ("bwd_cpt" is accepted and ignored); some defaults
+ * are mirrored in _lib.DEFAULT_TUNING and checked by tests/test_capi_symbols.py.  Process-wide (see Conventions). */
 int mvs_set_tuning(const char* key, int value);
 int mvs_get_tuning(const char* key, int* value);   /* the knob's current value (a freshly loaded library: its default) */
 

@@ -4,6 +4,7 @@ The product has NO fallback: if the HIP library is missing or fails to load, ``g
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -172,12 +173,32 @@ class MvsLib:
         self._mvs_launch_trace(buf, len(buf))
         return [s for s in buf.value.decode().split(",") if s]
 
+    def get_tuning(self, key: str) -> int:
+        """current value of a measurement knob (csrc/tuning.h lists them)"""
+        v = _i()
+        self.call("mvs_get_tuning", key.encode(), C.byref(v))
+        return v.value
+
+    @contextlib.contextmanager
+    def tuning(self, **knobs):
+        """``with lib.tuning(bwd_gd=0, bwd_dslab=4): ...`` -- the named knobs hold these values inside the block and are put back to
+        what they WERE (not to an assumed default) when it ends, also by an exception or an unknown key."""
+        old = []
+        try:
+            for key, val in knobs.items():
+                old.append((key, self.get_tuning(key)))
+                self.call("mvs_set_tuning", key.encode(), int(val))
+            yield self
+        finally:
+            for key, val in reversed(old):
+                self.call("mvs_set_tuning", key.encode(), val)
+
 
 _INSTANCE = None
 
-# library defaults of the measurement knobs (csrc: g_conv_c8, g_conv_xcd); MVS_TUNING="k8=2,xcd=0" overrides them
+# library defaults of some measurement knobs (csrc/tuning.h has them all); MVS_TUNING="k8=2,xcd=0" overrides them
 # for A/B runs of bench.py / tools without touching code
-DEFAULT_TUNING = {"k8": 7, "xcd": 1, "side_pre": 1, "conv_pers": 1, "conv_pers_min": 1024, "conv_pers_nw": 8, "wgrad_pers": 1, "conv_small": 1, "tr2pw": 1, "sweep_bwd": 0, "wgrad_small": 0, "wgrad_groups": 768, "wgrad8_groups": 192, "wgrad8_gs": 2, "wgrad8_nch": 2, "cout1_h4": 1, "wgrad2d_batch": 2048}
+DEFAULT_TUNING = {"k8": 7, "xcd": 1, "side_pre": 1, "conv_pers": 1, "conv_pers_min": 1024, "conv_pers_nw": 8, "wgrad_pers": 1, "conv_small": 1, "tr2pw": 1, "sweep_bwd": 0, "wgrad_small": 0, "wgrad_groups": 768, "wgrad8_groups": 192, "wgrad8_gs": 2, "wgrad8_nch": 2, "cout1_h4": 1, "wgrad2d_batch": 2048, "sweep_fwd": 3}
 
 
 def get() -> MvsLib:

@@ -888,10 +888,7 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_batch_reduce_kernel(Wg2Batch
 // host side
 // ------------------------------------------------------------------------------------------------
 static const int C2_WGRAD_GROUPS = 1024;  // partial images the workspace holds
-int g_conv2d_wgrad_groups = 256;          // tuning knob "wgrad2d_groups" (<= 1024): persistent workgroups of the weight gradient (256 = one per CU;
-                                          // more let a CU overlap one workgroup's tile staging with another's MFMA loop -- not yet measured)
-int g_conv2d_pp = 1;        // tuning knob "conv2d_pp": 3x3 stride-1 layers with <= 8 output channels as pixel-pair GEMMs (conv2d_igemm_kernel<.., PP>)
-int g_conv2d_s2_mfma = 2;   // tuning knob "conv2d_s2_mfma": stride-2 input gradient as ONE four-class MFMA pass with compacted taps (2, round 6), four parity-class passes (1), direct VALU form (0)
+// (knob "wgrad2d_groups": 256 = one per CU; more let a CU overlap one workgroup's tile staging with another's MFMA loop -- not yet measured)
 
 static bool c2_shape_ok(int ks, int stride) { return (ks == 3 && stride == 1) || (ks == 5 && stride == 2); }
 static int c2_cc(int ks, int cin) { return ks == 5 ? 8 : (cin <= 4 ? 4 : (cin <= 8 ? 8 : (cin <= 16 ? 16 : 32))); }
@@ -903,7 +900,7 @@ extern "C" long long mvs_conv2d_workspace_floats(int op, int N, int H, int W, in
         const int cxs = Cin > 32 ? 32 : (Cin + 3) / 4 * 4, cgs = Cout > 32 ? 32 : (Cout + 15) / 16 * 16;
         // one partial image per persistent workgroup the launch will actually use (knob "wgrad2d_groups", evaluated now: the
         // caller queries the size right before the call), not the 1024-image ceiling (37.7 MB instead of 9.4 MB per 32x32 layer)
-        const int gq = g_conv2d_wgrad_groups < 1 ? 1 : (g_conv2d_wgrad_groups > C2_WGRAD_GROUPS ? C2_WGRAD_GROUPS : g_conv2d_wgrad_groups);
+        const int gq = g_tune.wgrad2d_groups < 1 ? 1 : (g_tune.wgrad2d_groups > C2_WGRAD_GROUPS ? C2_WGRAD_GROUPS : g_tune.wgrad2d_groups);
         return (long long)gq * nt * cxs * cgs;
     }
     const int ci = op == 1 ? Cout : Cin, co = op == 1 ? Cin : Cout;   // an input gradient is a forward-style pass on gy
@@ -941,7 +938,7 @@ static void c2_launch(const Conv2dArgs& a, int nb, dim3 grid, hipStream_t st) {
 static void c2_fwd_pack_plan(int Cin, int Cout, int ks, int stride, Pack2dItem& it) {
     const int cc = c2_cc(ks, Cin), nt = ks * ks, nch = mvs_cdiv(Cin, cc);
     it.NT = nt; it.CC = cc; it.Cin = Cin; it.Cout = Cout;
-    if (ks == 3 && stride == 1 && Cout <= 8 && (cc == 4 || cc == 8) && g_conv2d_pp) {
+    if (ks == 3 && stride == 1 && Cout <= 8 && (cc == 4 || cc == 8) && g_tune.conv2d_pp) {
         it.pp = 1; it.NB = 1; it.total = nch * c2_ksteps(12, cc) * 256;
     } else {
         it.pp = 0; it.NB = mvs_cdiv(Cout, 16); it.total = nch * c2_ksteps(nt, cc) * it.NB * 256;
@@ -961,7 +958,7 @@ static int c2_run_igemm(const float* x, const float* w, const float* bias, float
     a.nth = mvs_cdiv(a.Ho, 8); a.ntw = mvs_cdiv(a.Wo, 32);
     const int cc = c2_cc(ks, Cin), nt = ks * ks, nch = mvs_cdiv(Cin, cc);
     a.nb_total = mvs_cdiv(Cout, 16);
-    if (ks == 3 && stride == 1 && Cout <= 8 && (cc == 4 || cc == 8) && g_conv2d_pp) {
+    if (ks == 3 && stride == 1 && Cout <= 8 && (cc == 4 || cc == 8) && g_tune.conv2d_pp) {
         // narrow layers (3 -> 8, 8 -> 8 of FeatureNet): pixel pairs fill the MFMA's 16 columns (knob "conv2d_pp")
         const int totalp = nch * c2_ksteps(12, cc) * 256;
         if (!ws_packed)
@@ -1121,7 +1118,7 @@ extern "C" int mvs_conv2d_dgrad_wl(const float* gy, const float* w, float* gx, f
     MVS_REQUIRE(gy && w && gx && ws, MVS_ERR_NULL, "conv2d_dgrad: null pointer argument");
     w_channels_last = w_channels_last ? 1 : 0;
     if (stride == 1) return c2_run_igemm(gy, w, nullptr, gx, ws, N, H, W, Cout, Cin, ks, 1, 1, stream, 0, 0.f, nullptr, 0, 1, 0, nullptr, nullptr, nullptr, w_channels_last);
-    if (g_conv2d_s2_mfma == 2) {
+    if (g_tune.conv2d_s2_mfma == 2) {
         // round 6: the four parity classes in ONE pass (class = blockIdx.z) behind ONE pack launch, compacted taps (25 tap slices, not 36)
         const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
         const int cc = c2_cc(3, Cout), nch = mvs_cdiv(Cout, cc), nbt = mvs_cdiv(Cin, 16);
@@ -1141,7 +1138,7 @@ extern "C" int mvs_conv2d_dgrad_wl(const float* gy, const float* w, float* gx, f
 #undef MVS_S2D_CASE
         return mvs_check_launch("conv2d_dgrad_s2_one_pass");
     }
-    if (g_conv2d_s2_mfma) {
+    if (g_tune.conv2d_s2_mfma) {
         // four parity classes, each a 3x3 stride-1 pass over gy on the coarse grid with its own (partly empty) weight image
         const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
         const int cc = c2_cc(3, Cout), nch = mvs_cdiv(Cout, cc), nbt = mvs_cdiv(Cin, 16);
@@ -1185,7 +1182,7 @@ extern "C" int mvs_conv2d_wgrad(const float* x, const float* gy, float* gw, floa
     if (rc) return rc;
     MVS_REQUIRE(x && gy && gw && ws, MVS_ERR_NULL, "conv2d_wgrad: null pointer argument");
     const int Ho = stride == 1 ? H : (H - 1) / 2 + 1, Wo = stride == 1 ? W : (W - 1) / 2 + 1;
-    const int gmax = g_conv2d_wgrad_groups < 1 ? 1 : (g_conv2d_wgrad_groups > C2_WGRAD_GROUPS ? C2_WGRAD_GROUPS : g_conv2d_wgrad_groups);
+    const int gmax = g_tune.wgrad2d_groups < 1 ? 1 : (g_tune.wgrad2d_groups > C2_WGRAD_GROUPS ? C2_WGRAD_GROUPS : g_tune.wgrad2d_groups);
     const int nt = ks * ks;
     // layers wider than 32 channels (the feature pyramid's 64) run as <= 32 x <= 32 channel slices, one after the other
     for (int ci0 = 0; ci0 < Cin; ci0 += 32)
@@ -1224,7 +1221,8 @@ extern "C" int mvs_conv2d_wgrad(const float* x, const float* gy, float* gw, floa
 }
 
 // ---- all layers' weight gradients in one launch -------------------------------------------------------------------------------
-int g_conv2d_wgrad_batch_groups = 2048;   // tuning knob "wgrad2d_batch": workgroups of the batched weight gradient (both launches together), shared out by work; FeatureNet at config 2: 0.185 / 0.180 / 0.176 / 0.174 / 0.176 ms at 1024 / 1536 / 2048 / 3072 / 4096 (profiles/r04_run29_*)
+// knob "wgrad2d_batch": workgroups of the batched weight gradient (both launches together), shared out by work; FeatureNet at config 2:
+// 0.185 / 0.180 / 0.176 / 0.174 / 0.176 ms at 1024 / 1536 / 2048 / 3072 / 4096 (profiles/r04_run29_*)
 
 struct Wg2Static { int ks, stride, cx, cgmax, th, rowsp, cgp, cost; };
 template <class C>
@@ -1262,7 +1260,7 @@ static long long wg2_plan(int n, const int* shapes, Wg2Batch& b) {
         cost[i] = (double)L.ntiles * T.cost;
         total += cost[i];
     }
-    const int budget = g_conv2d_wgrad_batch_groups < n ? n : (g_conv2d_wgrad_batch_groups > 4096 ? 4096 : g_conv2d_wgrad_batch_groups);
+    const int budget = g_tune.wgrad2d_batch < n ? n : (g_tune.wgrad2d_batch > 4096 ? 4096 : g_tune.wgrad2d_batch);
     long long floats = 0;
     int wgc[2] = {0, 0}, rb = 0;       // workgroup ranges per launch class (conv2d_wgrad_batch_kernel<0 / 1>)
     for (int i = 0; i < n; ++i) {

@@ -15,13 +15,6 @@
 #include "mvs_rt.h"
 #include "conv_map.h"
 
-// tuning knob "cout1_d4", bit 1: the Cout = 1 layer of the bf16 inference path with four outputs per thread (conv3d_bf16.hip:
-// 0.426 -> 0.368 ms -- on).  The fp32 forms of the same idea (bit 0 in round 3) measured slower (profiles/r03_run16_*: forward
-// 0.089 -> 0.091 ms, 16 channels 0.331 -> 0.473, input gradient 0.083 -> 0.107) and were removed in round 4.
-int g_conv_cout1_d4 = 2;
-
-extern int g_conv_split, g_conv_small, g_conv_small_wgs, g_conv_tr2pw;
-
 #include "conv_args.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -1481,10 +1474,8 @@ static int pick_cc(int geom, int cin) {
 // gradient; 32 -> 32 at 48x32x40 0.052 -> 0.062; 32 -> 64 stride 2 0.034 -> 0.058; step 4.699 -> 4.871 ms (profiles/r06_run11_*).  The
 // small chunks ARE the pipeline of these launches: 24 KB of LDS per workgroup lets several workgroups share a CU and overlap each other's
 // stage / MFMA phases, while a 78-128 KB tile leaves one workgroup per CU alone with a 28-load staging phase and nothing to hide it.
-int g_conv_cc_wide = 0;
-int g_conv_cin1_vpt = 1;   // tuning knob "cin1_vpt": voxels per thread of the Cout == 1 layer's input gradient (1 = default; 4 = four from 1 M voxels on, 5 = always four).  MEASURED AND REJECTED (round 6, profiles/r06_run13_*): four voxels per thread amortise the wave reduction of the backward statistics but serialise the loads of a quarter as many workgroups: 0.090 -> 0.123 ms, step 4.726 -> 4.749
 static int pick_cc_k(int geom, int kgeom, int cin) {
-    if (g_conv_cc_wide) {
+    if (g_tune.cc_wide) {
         if (kgeom == GEOM_S1_SMALL && (cin == 32 || cin == 64)) return cin;
         if (kgeom == GEOM_S2_SMALL && (cin == 16 || cin == 32)) return cin;
     }
@@ -1497,34 +1488,6 @@ static size_t packed_floats(int geom, int cin, int cout) {
     if (nb == 3) nb = 4;
     return (size_t)total_ksteps(geom, cin, cc) * nb * 256;
 }
-
-int g_conv_split = 1;       // tuning knob "conv_split" (mvs_set_tuning): 0 keeps all Cout tiles in one workgroup
-int g_conv_tr2pw = 1;       // tuning knob "tr2pw": transposed stride-2 conv with Cout == 8 as W-parity-merged GEMMs (GEOM_TR2_PW)
-int g_conv_small_wgs = 384;   // tuning knob "conv_small_wgs": quarter-size tiles below this many workgroups (~1.5 per CU)
-int g_conv_small = 1;   // tuning knob "conv_small": quarter-size workgroup tiles for under-filled launches (0 never, 1 auto, 2 always)
-int g_conv_c8 = 7;      // tuning knob "k8", bit mask: 1|2 = Cout==8 stride-1 layers run the 4x4x1 MFMA forward with the weights as the broadcast operand (0: generic kernel), +4 = weight gradient with g as the broadcast operand
-int g_conv_wgrad_groups = 768;   // tuning knob "wgrad_groups": persistent workgroups of the generic weight-gradient kernels (<= 768)
-int g_conv_cout1_h4 = 1;         // tuning knob "cout1_h4": the 8 -> 1 layer with four outputs per thread (conv_cout1_h4_kernel); 0: one output per thread
-int g_conv_wgrad8_groups = 192;  // tuning knob "wgrad8_groups": ... of the CG == 8 kernel (conv0; <= 512).  On the side stream it runs under the plane-sweep backward and the 2-D extractor's backward.  While the main stream was the longer one the step was faster the less this kernel took from it (5.440 ms at 512, 5.416 at 384, 5.413 at 256, 5.400 at 128: profiles/r04_run9_*); since the extractor's weight gradients became one launch the side stream ends last (+0.05 ms at the join) and 192 is the best of 128 / 192 / 256 / 384 / 512 (5.28 / 5.23 / 5.25 / 5.24 / 5.28: profiles/r04_run25_*); round 5, conv_c8_wgrad_gs_kernel (sixteen waves, 106 KB of LDS per workgroup): 4.77 ms/step at 192, 4.78 at 176 / 160, 4.79 at 224, 4.83 at 256, 4.85 at 128 (profiles/r05_final_session.log, r05_run33_*)
-int g_conv_wgrad8_nch = 2;       // tuning knob "wgrad8_nch": 2 = the CG == 8 weight gradient stages both 16-channel chunks of a 32-channel X in one workgroup.  Default since the end of round 4: at 192 workgroups the one-chunk form draws 2.31 GB from HBM per launch (0.63 GB algorithmic; 1.14 GB at 128 workgroups, 2.04 GB at 256: which halo lines neighbouring workgroups find in their XCD's L2 depends on the count), the two-chunk form 1.08 GB, at the same step time (5.313 vs 5.298 ms, profiles/r04_run31_*); alone on the GPU it is the slower kernel (0.85 vs 0.76 ms at 192 workgroups)
-int g_conv_wgrad_small = 0;   // tuning knob "wgrad_small": 1 = quarter-size tiles in the generic weight-gradient kernel for 8-channel / stride-2 layers with many tiles, 2 = for every layer with many tiles, 3 = always (tests)
-int g_conv_side_pre = 1;   // tuning knob "side_pre": one-Cout-tile kernels with epilogue side inputs (skip / bn_raw) request them before the k-loop (1) or at the top of the epilogue (0)
-int g_conv_pers = 1;    // tuning knob "conv_pers": 1 = one-chunk layers (16 -> <= 16, 8 -> 32 stride 1; 8 -> <= 16 stride 2) run conv3d_pers.hip
-int g_conv_pers_min_wgs = 1024;   // tuning knob "conv_pers_min": ... when the one-tile kernel would launch at least this many workgroups (a persistent grid needs several tiles per workgroup)
-int g_conv_wgrad_pers = 1;   // tuning knob "wgrad_pers"
-bool conv_wgrad_pers_serves(int geom, int CX, int CG);
-int run_conv_wgrad_pers(int geom, const WgradArgs& a, int max_groups, hipStream_t st);
-bool conv_c8_wgrad_gs_serves(int geom, int CX, int CG);
-int run_conv_c8_wgrad_gs(const WgradArgs& a, int max_groups, int waves, hipStream_t st);
-int g_conv_wgrad8_gs = 2;   // tuning knob "wgrad8_gs": conv0's weight gradient in the output-gradient-shifted form on the 16x16x4 MFMA (conv3d_pers.hip: conv_c8_wgrad_gs_kernel); 1: eight waves per workgroup, 2: sixteen (0.463 / 0.447 ms alone); 0: conv_c8_wgrad_kernel (4x4x1 MFMA, X shifted)
-bool conv_pers_serves(int geom, int cin, int cout);
-int run_conv_pers(int geom, const ConvArgs& a, hipStream_t st);
-bool conv_x3_serves(int geom, const ConvArgs& a);       // conv3d_x3.hip (knob "conv0_x3", opt-in)
-int run_conv_x3(const ConvArgs& a, const float* w, int wlayout, int flip, hipStream_t st);
-bool conv_x3_fwd_serves(int geom, const ConvArgs& a);
-int run_conv_x3_fwd(const ConvArgs& a, const float* w, int wlayout, int flip, float* ws, hipStream_t st);
-extern int g_conv_x3;
-int g_conv_xcd = 1;     // tuning knob "xcd": XCD-aware tile order in the broadcast-operand forward and the Cout == 8 weight gradient
 
 // launch-check labels (error messages, and the launch trace the tests read: mvs_launch_trace) say which size-selected arm ran
 template <int GEOM>
@@ -1540,7 +1503,7 @@ static int launch_igemm_nb(const ConvArgs& a, int NB, int nblocks, hipStream_t s
     if (a.skip || a.bn_raw) {
         switch (NB) {
             case 1:
-                if (g_conv_side_pre) MVS_LAUNCH((conv_igemm_kernel<GEOM, CC, 1, 2>), grid, block, 0, st, a);
+                if (g_tune.side_pre) MVS_LAUNCH((conv_igemm_kernel<GEOM, CC, 1, 2>), grid, block, 0, st, a);
                 else MVS_LAUNCH((conv_igemm_kernel<GEOM, CC, 1, 1>), grid, block, 0, st, a);
                 break;
             case 2: MVS_LAUNCH((conv_igemm_kernel<GEOM, CC, 2, 1>), grid, block, 0, st, a); break;
@@ -1565,13 +1528,13 @@ static void igemm_tiling(int geom, int B, int QD, int QH, int QW, int cout, int&
     const int nb_total = mvs_cdiv(cout, 16) == 3 ? 4 : mvs_cdiv(cout, 16);
     nblocks = B * mvs_cdiv(QD, geom_tqd(geom)) * mvs_cdiv(QH, geom_tqh(geom)) * mvs_cdiv(QW, 16);
     NB = nb_total;
-    if (g_conv_split && nblocks < 512 && NB > 1) NB = 1;
+    if (g_tune.conv_split && nblocks < 512 && NB > 1) NB = 1;
     kgeom = geom;
     // measured per geometry (profiles/r02_run14_*): stride-2 layers gain ~10 % from quarter tiles at every size of the network
     // (5x9x33-voxel halo in LDS -> 3x9x33: one more workgroup per CU), stride-1 layers up to ~1000 workgroups, the transposed
     // geometry only when the chip is under-filled (its 8 parity classes re-walk the tile: smaller tiles lose 10 % at L0)
-    const long thr = (long)g_conv_small_wgs * (geom == GEOM_S2 ? 24 : (geom == GEOM_S1 ? 3 : 1));
-    if (g_conv_small == 2 || (g_conv_small == 1 && (long)nblocks * (nb_total / NB) < thr)) {
+    const long thr = (long)g_tune.conv_small_wgs * (geom == GEOM_S2 ? 24 : (geom == GEOM_S1 ? 3 : 1));
+    if (g_tune.conv_small == 2 || (g_tune.conv_small == 1 && (long)nblocks * (nb_total / NB) < thr)) {
         kgeom = geom + GEOM_S1_SMALL;
         nblocks = B * mvs_cdiv(QD, geom_tqd(kgeom)) * mvs_cdiv(QH, geom_tqh(kgeom)) * mvs_cdiv(QW, 16);
     }
@@ -1645,7 +1608,7 @@ static void plan_grid(const IgemmPlan& p, int& QD, int& QH, int& QW) {
     else { QD = p.Di; QH = p.Hi; QW = p.Wi; }
 }
 static bool plan_is_c8(const IgemmPlan& p, const Epilogue* ep) {
-    return (g_conv_c8 & 3) && p.geom == GEOM_S1 && p.cout == 8 && (p.cin == 8 || p.cin == 16 || p.cin == 32) && !(ep && ep->bn_raw);
+    return (g_tune.k8 & 3) && p.geom == GEOM_S1 && p.cout == 8 && (p.cin == 8 || p.cin == 16 || p.cin == 32) && !(ep && ep->bn_raw);
 }
 static bool plan_is_cout1(const IgemmPlan& p, const Epilogue* ep) {
     return p.geom == GEOM_S1 && p.cout == 1 && p.wlayout == WL_OIK && !p.flip && (p.cin == 8 || p.cin == 16) &&
@@ -1672,7 +1635,7 @@ static int plan_pack(const IgemmPlan& p, const float* w, float* ws, PackItem& it
     igemm_tiling(p.geom, p.B, QD, QH, QW, p.cout, kgeom, NB, nblocks);
     const int cc = pick_cc_k(p.geom, kgeom, p.cin);
     const int nb_total = mvs_cdiv(p.cout, 16) == 3 ? 4 : mvs_cdiv(p.cout, 16);
-    const int pgeom = (kgeom == GEOM_TR2 && cc == 16 && p.cout == 8 && g_conv_tr2pw) ? GEOM_TR2_PW : p.geom;
+    const int pgeom = (kgeom == GEOM_TR2 && cc == 16 && p.cout == 8 && g_tune.tr2pw) ? GEOM_TR2_PW : p.geom;
     it.kind = 0; it.geom = pgeom; it.CC = cc; it.Cin = p.cin; it.Cout = p.cout; it.NB = nb_total; it.layout = p.wlayout; it.flip = p.flip;
     it.total = (int)((size_t)total_ksteps(pgeom, p.cin, cc) * nb_total * 256);
     return MVS_OK;
@@ -1709,25 +1672,25 @@ static int run_igemm(const IgemmPlan& p, const float* in, const float* wsrc, flo
     else if (geom == GEOM_S2) { a.Do = a.QD; a.Ho = a.QH; a.Wo = a.QW; }
     else { a.Do = 2 * p.Di; a.Ho = 2 * p.Hi; a.Wo = 2 * p.Wi; }
     a.ntd = mvs_cdiv(a.QD, geom_tqd(geom)); a.nth = mvs_cdiv(a.QH, geom_tqh(geom)); a.ntw = mvs_cdiv(a.QW, 16);
-    if ((g_conv_x3 & 1) && conv_x3_serves(geom, a)) return run_conv_x3(a, wsrc, p.wlayout, p.flip, st);   // opt-in: split-bf16 products
-    if ((g_conv_x3 & 2) && conv_x3_fwd_serves(geom, a)) return run_conv_x3_fwd(a, wsrc, p.wlayout, p.flip, ws, st);
+    if ((g_tune.conv0_x3 & 1) && conv_x3_serves(geom, a)) return run_conv_x3(a, wsrc, p.wlayout, p.flip, st);   // opt-in: split-bf16 products
+    if ((g_tune.conv0_x3 & 2) && conv_x3_fwd_serves(geom, a)) return run_conv_x3_fwd(a, wsrc, p.wlayout, p.flip, ws, st);
     if (plan_is_c8(p, &ep)) {
         // 4x4x1 MFMA with the weights as the broadcast operand, tile 4 x 4 x 16 positions (reads the parameter tensor itself)
         const int ntl = B * a.ntd * a.nth * a.ntw;
         const int nbc = ntl < 512 ? ntl : 512;            // 80 KB of LDS -> 2 resident workgroups per CU
-        if (cin == 32) MVS_LAUNCH((conv_c8_fwd_bc_kernel<16, 2>), dim3(nbc), dim3(256), 0, st, a, wsrc, p.wlayout, p.flip, g_conv_xcd);
-        else if (cin == 16) MVS_LAUNCH((conv_c8_fwd_bc_kernel<16, 1>), dim3(nbc), dim3(256), 0, st, a, wsrc, p.wlayout, p.flip, g_conv_xcd);
-        else MVS_LAUNCH((conv_c8_fwd_bc_kernel<8, 1>), dim3(nbc), dim3(256), 0, st, a, wsrc, p.wlayout, p.flip, g_conv_xcd);
+        if (cin == 32) MVS_LAUNCH((conv_c8_fwd_bc_kernel<16, 2>), dim3(nbc), dim3(256), 0, st, a, wsrc, p.wlayout, p.flip, g_tune.xcd);
+        else if (cin == 16) MVS_LAUNCH((conv_c8_fwd_bc_kernel<16, 1>), dim3(nbc), dim3(256), 0, st, a, wsrc, p.wlayout, p.flip, g_tune.xcd);
+        else MVS_LAUNCH((conv_c8_fwd_bc_kernel<8, 1>), dim3(nbc), dim3(256), 0, st, a, wsrc, p.wlayout, p.flip, g_tune.xcd);
         return mvs_check_launch("conv_c8_fwd_bc");
     }
     int nblocks = B * a.ntd * a.nth * a.ntw;
     if (plan_is_cout1(p, &ep)) {
-        if (cin == 8 && g_conv_cout1_h4) {
+        if (cin == 8 && g_tune.cout1_h4) {
             a.ntd = mvs_cdiv(a.QD, CO1_TD); a.nth = mvs_cdiv(a.QH, CO1_TH); a.ntw = mvs_cdiv(a.QW, CO1_TW);
             MVS_LAUNCH(conv_cout1_h4_kernel, dim3(B * a.ntd * a.nth * a.ntw), dim3(256), 0, st, a, wsrc);
         } else if (cin == 8) MVS_LAUNCH((conv_cout1_kernel<8>), dim3(nblocks), dim3(256), 0, st, a, wsrc);
         else MVS_LAUNCH((conv_cout1_kernel<16>), dim3(nblocks), dim3(256), 0, st, a, wsrc);
-        return mvs_check_launch(cin == 8 ? (g_conv_cout1_h4 ? "conv_cout1 h4" : "conv_cout1 cin=8") : "conv_cout1 cin=16");
+        return mvs_check_launch(cin == 8 ? (g_tune.cout1_h4 ? "conv_cout1 h4" : "conv_cout1 cin=8") : "conv_cout1 cin=16");
     }
     int NB, kgeom;
     a.nb_total = mvs_cdiv(cout, 16) == 3 ? 4 : mvs_cdiv(cout, 16);
@@ -1747,13 +1710,13 @@ static int run_igemm(const IgemmPlan& p, const float* in, const float* wsrc, flo
     }
     a.wp = ws;
     // knob "conv_pers": single-chunk layers with a small weight image through the persistent LDS-DMA kernel (conv3d_pers.hip)
-    if (g_conv_pers && conv_pers_serves(geom, cin, cout) && (long)nblocks * (a.nb_total / NB) >= g_conv_pers_min_wgs) {
+    if (g_tune.conv_pers && conv_pers_serves(geom, cin, cout) && (long)nblocks * (a.nb_total / NB) >= g_tune.conv_pers_min) {
         a.ntd = mvs_cdiv(a.QD, geom_tqd(geom)); a.nth = mvs_cdiv(a.QH, geom_tqh(geom));
         return run_conv_pers(geom, a, st);
     }
     // (the transposed 16 -> 8 layers: conv11 forward, conv1's input gradient -- when the W-parity-merged image was packed)
-    if ((g_conv_pers & 1) && kgeom == GEOM_TR2 && cc == 16 && cout == 8 && g_conv_tr2pw && conv_pers_serves(GEOM_TR2_PW, cin, cout) &&
-        nblocks >= g_conv_pers_min_wgs)
+    if ((g_tune.conv_pers & 1) && kgeom == GEOM_TR2 && cc == 16 && cout == 8 && g_tune.tr2pw && conv_pers_serves(GEOM_TR2_PW, cin, cout) &&
+        nblocks >= g_tune.conv_pers_min)
         return run_conv_pers(GEOM_TR2_PW, a, st);
     if (kgeom == GEOM_S1) return cc == 16 ? launch_igemm_nb<GEOM_S1, 16>(a, NB, nblocks, st)
                                           : launch_igemm_nb<GEOM_S1, 8>(a, NB, nblocks, st);
@@ -1773,7 +1736,7 @@ static int run_igemm(const IgemmPlan& p, const float* in, const float* wsrc, flo
         if (cc == 32) return launch_igemm_nb<GEOM_TR2_SMALL, 32>(a, NB, nblocks, st);
         return launch_igemm_nb<GEOM_TR2_SMALL, 64>(a, NB, nblocks, st);
     }
-    if (cc == 16 && cout == 8 && g_conv_tr2pw) return launch_igemm_nb<GEOM_TR2_PW, 16>(a, NB, nblocks, st);
+    if (cc == 16 && cout == 8 && g_tune.tr2pw) return launch_igemm_nb<GEOM_TR2_PW, 16>(a, NB, nblocks, st);
     if (cc == 16) return launch_igemm_nb<GEOM_TR2, 16>(a, NB, nblocks, st);
     if (cc == 32) return launch_igemm_nb<GEOM_TR2, 32>(a, NB, nblocks, st);
     return launch_igemm_nb<GEOM_TR2, 64>(a, NB, nblocks, st);
@@ -1799,7 +1762,10 @@ static int run_cin1(const IgemmPlan& p, const float* gy, const float* w, float* 
     }
     const size_t total = (size_t)p.B * p.Di * p.Hi * p.Wi;
     // knob "cin1_vpt": 4 = four voxels per thread from 1 M voxels on (small volumes keep one: they need the workgroups), 5 = always (tests), 1 = never
-    const int vpt = (g_conv_cin1_vpt == 5 || (g_conv_cin1_vpt == 4 && total >= (size_t)1 << 20)) ? 4 : 1;
+    // knob "cin1_vpt" (1 = default; 4 = four from 1 M voxels on, 5 = always four).  MEASURED AND REJECTED (round 6, profiles/r06_run13_*):
+    // four voxels per thread amortise the wave reduction of the backward statistics but serialise the loads of a quarter as many
+    // workgroups: 0.090 -> 0.123 ms, step 4.726 -> 4.749
+    const int vpt = (g_tune.cin1_vpt == 5 || (g_tune.cin1_vpt == 4 && total >= (size_t)1 << 20)) ? 4 : 1;
     dim3 grid((unsigned)((total + 256 * vpt - 1) / (256 * vpt)));
     if (C == 8 && vpt == 4) MVS_LAUNCH((conv_cin1_kernel<8, 4>), grid, dim3(256), 0, st, gy, (const float*)ws, gx, p.B, p.Di, p.Hi, p.Wi, ep.bn_raw, ep.bn_stats, ep.slots, ep.nslots);
     else if (C == 8) MVS_LAUNCH((conv_cin1_kernel<8, 1>), grid, dim3(256), 0, st, gy, (const float*)ws, gx, p.B, p.Di, p.Hi, p.Wi, ep.bn_raw, ep.bn_stats, ep.slots, ep.nslots);
@@ -1825,7 +1791,7 @@ static int run_wgrad(int geom, const float* X, const float* Gt, float* gw, float
                 "conv wgrad: X channels must be 8/16/32/64, got %d", CX);
     MVS_REQUIRE(CG >= 1 && CG <= 64, MVS_ERR_UNSUPPORTED, "conv wgrad: G channels must be <= 64, got %d", CG);
     WgradArgs a = {};
-    a.x = X; a.g = Gt; a.part = ws; a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.CX = CX; a.CG = CG; a.xcd = g_conv_xcd;
+    a.x = X; a.g = Gt; a.part = ws; a.B = B; a.Di = Di; a.Hi = Hi; a.Wi = Wi; a.CX = CX; a.CG = CG; a.xcd = g_tune.xcd;
     if (geom == GEOM_S1) { a.QD = Di; a.QH = Hi; a.QW = Wi; }
     else { a.QD = (Di - 1) / 2 + 1; a.QH = (Hi - 1) / 2 + 1; a.QW = (Wi - 1) / 2 + 1; }
     a.ntd = mvs_cdiv(a.QD, geom == GEOM_S2 ? 2 : 4); a.nth = mvs_cdiv(a.QH, 4); a.ntw = mvs_cdiv(a.QW, 16);
@@ -1834,32 +1800,43 @@ static int run_wgrad(int geom, const float* X, const float* Gt, float* gw, float
     const int nbw = CG > 16 ? 2 : 1;
     // knobs "wgrad_groups" / "wgrad8_groups": persistent workgroups of a launch.  The weight gradients run on a side stream next
     // to the backward pass's critical path; fewer workgroups take longer but leave more of the chip to the main stream.
-    const int maxg = g_conv_wgrad_groups < 1 ? 1 : (g_conv_wgrad_groups > WGRAD_MAX_GROUPS ? WGRAD_MAX_GROUPS : g_conv_wgrad_groups);
+    const int maxg = g_tune.wgrad_groups < 1 ? 1 : (g_tune.wgrad_groups > WGRAD_MAX_GROUPS ? WGRAD_MAX_GROUPS : g_tune.wgrad_groups);
     int groups = ntiles < maxg ? ntiles : maxg;
-    if (g_conv_c8 && geom == GEOM_S1 && CG == 8 && CX % 16 == 0) {
-        const int max8 = g_conv_wgrad8_groups < 1 ? 1 : (g_conv_wgrad8_groups > 512 ? 512 : g_conv_wgrad8_groups);
+    if (g_tune.k8 && geom == GEOM_S1 && CG == 8 && CX % 16 == 0) {
+        // knob "wgrad8_groups" (conv0; <= 512).  On the side stream it runs under the plane-sweep backward and the 2-D extractor's
+        // backward.  While the main stream was the longer one the step was faster the less this kernel took from it (5.440 ms at 512,
+        // 5.416 at 384, 5.413 at 256, 5.400 at 128: profiles/r04_run9_*); since the extractor's weight gradients became one launch the
+        // side stream ends last (+0.05 ms at the join) and 192 is the best of 128 / 192 / 256 / 384 / 512 (5.28 / 5.23 / 5.25 / 5.24 /
+        // 5.28: profiles/r04_run25_*); round 5, conv_c8_wgrad_gs_kernel (sixteen waves, 106 KB of LDS per workgroup): 4.77 ms/step at
+        // 192, 4.78 at 176 / 160, 4.79 at 224, 4.83 at 256, 4.85 at 128 (profiles/r05_final_session.log, r05_run33_*)
+        const int max8 = g_tune.wgrad8_groups < 1 ? 1 : (g_tune.wgrad8_groups > 512 ? 512 : g_tune.wgrad8_groups);
         const int g8 = ntiles < max8 ? ntiles : max8;   // 60 KB LDS -> 2 resident workgroups per CU
-        if (g_conv_wgrad8_gs && conv_c8_wgrad_gs_serves(geom, CX, CG)) {
-            const int np = run_conv_c8_wgrad_gs(a, g8, g_conv_wgrad8_gs == 1 ? 8 : 16, st);
+        // knob "wgrad8_gs": the output-gradient-shifted form with eight (1) or sixteen (2) waves per workgroup: 0.463 / 0.447 ms alone
+        if (g_tune.wgrad8_gs && conv_c8_wgrad_gs_serves(geom, CX, CG)) {
+            const int np = run_conv_c8_wgrad_gs(a, g8, g_tune.wgrad8_gs == 1 ? 8 : 16, st);
             if (np < 0) return np;
             return wgrad_finish(ws, np, CX, CG, gw, st);
         }
-        if (CX % 32 == 0 && g_conv_wgrad8_nch == 2) {     // both 16-channel chunks of a 32-channel line in one workgroup (knob "wgrad8_nch")
+        // knob "wgrad8_nch" = 2: default since the end of round 4: at 192 workgroups the one-chunk form draws 2.31 GB from HBM per launch
+        // (0.63 GB algorithmic; 1.14 GB at 128 workgroups, 2.04 GB at 256: which halo lines neighbouring workgroups find in their XCD's L2
+        // depends on the count), the two-chunk form 1.08 GB, at the same step time (5.313 vs 5.298 ms, profiles/r04_run31_*); alone on the
+        // GPU it is the slower kernel (0.85 vs 0.76 ms at 192 workgroups)
+        if (CX % 32 == 0 && g_tune.wgrad8_nch == 2) {     // both 16-channel chunks of a 32-channel line in one workgroup
             const int g2 = g8 > 256 ? 256 : g8;              // 110 KB of LDS: one workgroup per CU
-            if (g_conv_c8 & 4) MVS_LAUNCH((conv_c8_wgrad_kernel<true, 2>), dim3(g2, CX / 32), dim3(256), 0, st, a);
+            if (g_tune.k8 & 4) MVS_LAUNCH((conv_c8_wgrad_kernel<true, 2>), dim3(g2, CX / 32), dim3(256), 0, st, a);
             else MVS_LAUNCH((conv_c8_wgrad_kernel<false, 2>), dim3(g2, CX / 32), dim3(256), 0, st, a);
             int rc2 = mvs_check_launch("conv_c8_wgrad");
             if (rc2) return rc2;
             return wgrad_finish(ws, g2, CX, CG, gw, st);
         }
-        if (g_conv_c8 & 4) MVS_LAUNCH((conv_c8_wgrad_kernel<true, 1>), dim3(g8, CX / 16), dim3(256), 0, st, a);
+        if (g_tune.k8 & 4) MVS_LAUNCH((conv_c8_wgrad_kernel<true, 1>), dim3(g8, CX / 16), dim3(256), 0, st, a);
         else MVS_LAUNCH((conv_c8_wgrad_kernel<false, 1>), dim3(g8, CX / 16), dim3(256), 0, st, a);
         int rc8 = mvs_check_launch("conv_c8_wgrad");
         if (rc8) return rc8;
         return wgrad_finish(ws, g8, CX, CG, gw, st);
     }
     if (geom == GEOM_S1 && CG == 1 && (CX == 8 || CX == 16)) {
-        if (CX == 8 && g_conv_c8) MVS_LAUNCH(conv_wgrad_cg1_mfma_kernel, dim3(groups), dim3(256), 0, st, a);
+        if (CX == 8 && g_tune.k8) MVS_LAUNCH(conv_wgrad_cg1_mfma_kernel, dim3(groups), dim3(256), 0, st, a);
         else if (CX == 8) MVS_LAUNCH((conv_wgrad_cg1_kernel<8>), dim3(groups), dim3(256), 0, st, a);
         else MVS_LAUNCH((conv_wgrad_cg1_kernel<16>), dim3(groups), dim3(256), 0, st, a);
         int rc1 = mvs_check_launch("conv_wgrad_cg1");
@@ -1868,7 +1845,7 @@ static int run_wgrad(int geom, const float* X, const float* Gt, float* gw, float
     }
     // knob "wgrad_pers": one-chunk layers with <= 16 gradient channels and many tiles through the persistent LDS-DMA kernel
     // (conv3d_pers.hip): the level-0 / level-1 layers conv1, conv11 (stride 2, 8 X channels) and conv2 (stride 1, 16)
-    if (g_conv_wgrad_pers && conv_wgrad_pers_serves(geom, CX, CG) && ntiles >= g_conv_pers_min_wgs) {
+    if (g_tune.wgrad_pers && conv_wgrad_pers_serves(geom, CX, CG) && ntiles >= g_tune.conv_pers_min) {
         const int np = run_conv_wgrad_pers(geom, a, WGRAD_MAX_GROUPS, st);
         if (np < 0) return np;
         return wgrad_finish(ws, np, CX, CG, gw, st);
@@ -1876,8 +1853,8 @@ static int run_wgrad(int geom, const float* X, const float* Gt, float* gw, float
     // knob "wgrad_small": quarter-size tiles (the *_SMALL geometries) for the generic kernel when the launch has many tiles anyway:
     // a stride-2 layer with 8 X channels (the L0 layers) holds a 5x9x33-voxel halo + the G tile = 87 KB of LDS per workgroup, ONE
     // workgroup per CU; at 3x9x33 it is 51 KB and three fit (latency bound: 126 MB + 31 MB read in 99 us)
-    const bool small = g_conv_wgrad_small == 3 ||      // (3: always -- tests)
-                       (g_conv_wgrad_small && ntiles >= 2 * WGRAD_MAX_GROUPS && (g_conv_wgrad_small == 2 || cc == 8 || geom == GEOM_S2));
+    const bool small = g_tune.wgrad_small == 3 ||      // (3: always -- tests)
+                       (g_tune.wgrad_small && ntiles >= 2 * WGRAD_MAX_GROUPS && (g_tune.wgrad_small == 2 || cc == 8 || geom == GEOM_S2));
     if (small) {
         const int kg = geom + GEOM_S1_SMALL;
         a.ntd = mvs_cdiv(a.QD, geom_tqd(kg)); a.nth = mvs_cdiv(a.QH, geom_tqh(kg));

@@ -19,9 +19,6 @@
 #include "conv_map.h"
 
 typedef unsigned short bf16_t;
-extern int g_conv_cout1_d4;   // conv3d.hip: knob "cout1_d4"
-extern int g_conv_tr2pw;       // conv3d.hip: knob "tr2pw"
-int g_conv_bf16_dp = 1;         // knob "bf16_dp": conv0 of the bf16 path (32 -> 8) with two output depth slices per MFMA (GEOM_S1_DP)
 
 struct Bf16ConvArgs {
     const bf16_t* x;        // [B,Di,Hi,Wi,CIN] bf16
@@ -501,7 +498,10 @@ extern "C" int mvs_conv3d_bf16_fwd(const void* x, const float* w, void* y, void*
         a.QD = a.Do; a.QH = a.Ho; a.QW = a.Wo;
     } else { a.Do = 2 * D; a.Ho = 2 * H; a.Wo = 2 * W; a.QD = D; a.QH = H; a.QW = W; }
     a.ntd = mvs_cdiv(a.QD, geom == GEOM_S2 ? 2 : 4); a.nth = mvs_cdiv(a.QH, 4); a.ntw = mvs_cdiv(a.QW, 16);
-    if (geom == GEOM_S1 && Cout == 1 && (Cin == 8 || Cin == 16) && (g_conv_cout1_d4 & 2)) {   // direct form, four outputs per thread
+    // knob "cout1_d4", bit 1: the Cout = 1 layer with four outputs per thread: 0.426 -> 0.368 ms -- on.  The fp32 forms of the same idea
+    // (bit 0 in round 3) measured slower (profiles/r03_run16_*: forward 0.089 -> 0.091 ms, 16 channels 0.331 -> 0.473, input gradient
+    // 0.083 -> 0.107) and were removed in round 4.
+    if (geom == GEOM_S1 && Cout == 1 && (Cin == 8 || Cin == 16) && (g_tune.cout1_d4 & 2)) {   // direct form, four outputs per thread
         a.nth = mvs_cdiv(a.QH, 8);
         const long long nb4 = (long long)B * a.ntd * a.nth * a.ntw;
         MVS_REQUIRE(nb4 < (1ll << 31), MVS_ERR_SHAPE, "conv3d bf16: too many tiles");
@@ -512,8 +512,8 @@ extern "C" int mvs_conv3d_bf16_fwd(const void* x, const float* w, void* y, void*
     const int MB = mvs_cdiv(Cout, 16);
     // transposed with 8 output channels (16 -> 8, the last decoder block): both W parities in one MFMA (knob "tr2pw", shared with
     // the fp32 kernels' GEOM_TR2_PW)
-    const int kgeom = (geom == GEOM_TR2 && Cout == 8 && Cin == 16 && g_conv_tr2pw) ? GEOM_TR2_PW
-                    : ((geom == GEOM_S1 && Cout == 8 && Cin == 32 && g_conv_bf16_dp) ? GEOM_S1_DP : geom);   // knob "bf16_dp"
+    const int kgeom = (geom == GEOM_TR2 && Cout == 8 && Cin == 16 && g_tune.tr2pw) ? GEOM_TR2_PW
+                    : ((geom == GEOM_S1 && Cout == 8 && Cin == 32 && g_tune.bf16_dp) ? GEOM_S1_DP : geom);   // knob "bf16_dp"
     const int total = bf16_total_ksteps(kgeom, Cin) * MB * 512;
     MVS_LAUNCH(conv_bf16_pack_kernel, dim3(mvs_cdiv(total, 256)), dim3(256), 0, stream, w, (bf16_t*)ws, kgeom, Cin, Cout, MB,
                transposed ? WL_IOK : WL_OIK, total);

@@ -255,8 +255,6 @@ __global__ __launch_bounds__(NW * 64) void conv_pers_kernel(ConvArgs a) {
     }
 }
 
-int g_conv_pers_groups = 0;
-int g_conv_pers_nw = 8;
 // LDS bytes of an instantiation (host side: how many workgroups fit a CU)
 template <int GEOM, int CC, int NB>
 static int pers_lds_bytes() {
@@ -269,7 +267,7 @@ template <int GEOM, int CC, int NB, int NW>
 static int launch_pers(const ConvArgs& a, hipStream_t st) {
     const int ntiles = a.B * a.ntd * a.nth * a.ntw;
     const int per_cu = (160 * 1024) / pers_lds_bytes<GEOM, CC, NB>() >= 2 ? 2 : 1;
-    int groups = g_conv_pers_groups > 0 ? g_conv_pers_groups : 256 * per_cu;     // knob "conv_pers_groups" (tests: a few workgroups walk many tiles)
+    int groups = g_tune.conv_pers_groups > 0 ? g_tune.conv_pers_groups : 256 * per_cu;     // knob "conv_pers_groups" (tests: a few workgroups walk many tiles)
     if (groups > ntiles) groups = ntiles;
     dim3 grid(groups, a.nb_total / NB);
     if (a.skip || a.bn_raw) MVS_LAUNCH((conv_pers_kernel<GEOM, CC, NB, 1, NW>), grid, dim3(NW * 64), 0, st, a);
@@ -288,7 +286,7 @@ bool conv_pers_serves(int geom, int cin, int cout) {
 
 int run_conv_pers(int geom, const ConvArgs& a, hipStream_t st) {
     // knob "conv_pers_nw": waves per workgroup
-    if (g_conv_pers_nw == 8) {
+    if (g_tune.conv_pers_nw == 8) {
         if (geom == GEOM_S1 && a.Cin == 16) return launch_pers<GEOM_S1, 16, 1, 8>(a, st);
         if (geom == GEOM_S1 && a.Cin == 8) return launch_pers<GEOM_S1, 8, 2, 8>(a, st);
         if (geom == GEOM_S2 && a.Cin == 8) return launch_pers<GEOM_S2, 8, 1, 8>(a, st);
@@ -466,7 +464,7 @@ bool conv_wgrad_pers_serves(int geom, int CX, int CG) {
 // a: as run_wgrad fills it for the full-size tiles of `geom`; returns the number of partial images written (one per workgroup), < 0 on error
 int run_conv_wgrad_pers(int geom, const WgradArgs& a, int max_groups, hipStream_t st) {
     const int ntiles = a.B * a.ntd * a.nth * a.ntw;
-    int groups = g_conv_pers_groups > 0 ? g_conv_pers_groups : 256;       // 111-115 KB of LDS: one workgroup (8 waves) per CU
+    int groups = g_tune.conv_pers_groups > 0 ? g_tune.conv_pers_groups : 256;       // 111-115 KB of LDS: one workgroup (8 waves) per CU
     if (groups > ntiles) groups = ntiles;
     if (groups > max_groups) groups = max_groups;
     if (geom == GEOM_S1) MVS_LAUNCH((conv_wgrad_pers_kernel<GEOM_S1, 16>), dim3(groups), dim3(512), 0, st, a);

@@ -30,6 +30,18 @@ struct WgradArgs {
     int xcd;             // XCD-aware tile order (conv_c8_wgrad_kernel)
 };
 
+// what conv3d.hip's dispatch calls in the files of the size-selected arms
+bool conv_pers_serves(int geom, int cin, int cout);     // conv3d_pers.hip (knobs "conv_pers", "wgrad_pers", "wgrad8_gs")
+int run_conv_pers(int geom, const ConvArgs& a, hipStream_t st);
+bool conv_wgrad_pers_serves(int geom, int CX, int CG);
+int run_conv_wgrad_pers(int geom, const WgradArgs& a, int max_groups, hipStream_t st);
+bool conv_c8_wgrad_gs_serves(int geom, int CX, int CG);
+int run_conv_c8_wgrad_gs(const WgradArgs& a, int max_groups, int waves, hipStream_t st);
+bool conv_x3_serves(int geom, const ConvArgs& a);       // conv3d_x3.hip (knob "conv0_x3", opt-in)
+int run_conv_x3(const ConvArgs& a, const float* w, int wlayout, int flip, hipStream_t st);
+bool conv_x3_fwd_serves(int geom, const ConvArgs& a);
+int run_conv_x3_fwd(const ConvArgs& a, const float* w, int wlayout, int flip, float* ws, hipStream_t st);
+
 // ------------------------------------------------------------------------------------------------
 // XCD-aware tile order.  Workgroups are dealt round-robin to the 8 XCDs (each with its own 4 MB L2), so
 // xcd_block() gives every XCD one contiguous range of the tile order, and brick_tile() makes that order bricks

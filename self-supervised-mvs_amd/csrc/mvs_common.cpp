@@ -1,7 +1,8 @@
-// Error reporting + version for the C ABI (include/mvs_hip.h).  No exceptions cross the boundary:
+// Error reporting, launch trace, tuning knobs + version for the C ABI (include/mvs_hip.h).  No exceptions cross the boundary:
 // every entry point returns 0 or a negative code and leaves a message in a thread-local buffer.
 #include <stdarg.h>
 #include <stdio.h>
+#include <string.h>
 #include "mvs_rt.h"
 
 static thread_local char g_err[512] = "";
@@ -53,6 +54,42 @@ extern "C" int mvs_launch_trace(char* buf, int cap) {
     }
     return n;
 }
+
+// Measurement knobs: the values and the name table, both generated from the list in tuning.h.  Full-string keys: an unknown or
+// misspelt key is an error, never a silent hit on another knob.
+#define MVS_KNOB_DEFAULT(key, def, lo, hi, doc) def,
+MvsTuning g_tune = {MVS_KNOBS(MVS_KNOB_DEFAULT)};
+struct MvsKnob { const char* name; int* var; int lo, hi; };
+static const MvsKnob* mvs_find_knob(const char* key) {
+#define MVS_KNOB_ROW(key, def, lo, hi, doc) {#key, &g_tune.key, lo, hi},
+    static const MvsKnob knobs[] = {MVS_KNOBS(MVS_KNOB_ROW)};
+    for (const MvsKnob& k : knobs)
+        if (strcmp(key, k.name) == 0) return &k;
+    return nullptr;
+}
+extern "C" int mvs_set_tuning(const char* key, int value) {
+    MVS_REQUIRE(key, MVS_ERR_NULL, "mvs_set_tuning: null key");
+    const MvsKnob* k = mvs_find_knob(key);
+    if (!k) {
+        mvs_set_error("mvs_set_tuning: unknown key '%s'", key);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    *k->var = value < k->lo ? k->lo : (value > k->hi ? k->hi : value);
+    return MVS_OK;
+}
+// the knob's current value (bench.py --ab restores the LIBRARY's defaults after a toggle: tests/test_capi_symbols.py holds
+// _lib.DEFAULT_TUNING against the values a freshly loaded library reports)
+extern "C" int mvs_get_tuning(const char* key, int* value) {
+    MVS_REQUIRE(key && value, MVS_ERR_NULL, "mvs_get_tuning: null argument");
+    const MvsKnob* k = mvs_find_knob(key);
+    if (!k) {
+        mvs_set_error("mvs_get_tuning: unknown key '%s'", key);
+        return MVS_ERR_UNSUPPORTED;
+    }
+    *value = *k->var;
+    return MVS_OK;
+}
+
 extern "C" int mvs_version(void) { return 100; }  // 0.1.0
 extern "C" int mvs_is_emulation(void) {
 #if defined(MVS_CPU_EMUL)

@@ -112,6 +112,8 @@ typedef __attribute__((address_space(1))) double mvs_global_double;
     ((void)__hip_atomic_fetch_add((mvs_global_double*)(ptr), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
 #endif
 
+#include "tuning.h"   // g_tune: the measurement knobs the launchers read
+
 #define MVS_WAVE 64
 #define MVS_MAX_SRC 10
 

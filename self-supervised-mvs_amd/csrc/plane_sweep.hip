@@ -1365,91 +1365,13 @@ __global__ __launch_bounds__(256) MVS_WAVES_PER_SIMD(WPS) void plane_sweep_varia
 }
 
 // ------------------------------------------------------------------------------------------------
-// MVS_SWEEP_FWD=direct selects the tap-through-L1 kernel (kept for A/B measurements); default: LDS-staged
-// forward variants: 0 taps through L1 every plane, 1 LDS-staged windows, 2 register-cached taps (4 ch/thread),
-// 3 register-cached taps (8 ch/thread).  Default 3; MVS_SWEEP_FWD=<n> or mvs_set_tuning("sweep_fwd", n) for A/B.
-static int g_sweep_fwd_variant = -1;
-static int sweep_fwd_variant() {
-    if (g_sweep_fwd_variant < 0) {
-        const char* e = getenv("MVS_SWEEP_FWD");
-        g_sweep_fwd_variant = (e && e[0] >= '0' && e[0] <= '4') ? e[0] - '0' : 3;
-    }
-    return g_sweep_fwd_variant;
-}
-static int g_sweep_nt = 0;
-static int g_sweep_tile_w = 0;   // knob "tile_w": 0 = default square-ish tile
-static int g_sweep_dslab = 0;    // knob "dslab": planes per workgroup of the forward kernels, 0 = auto
-extern int g_conv_split;
-extern int g_conv_small;
-extern int g_conv_small_wgs;
-extern int g_conv_tr2pw;
-extern int g_conv_cc_wide;
-extern int g_conv_cin1_vpt;
-extern int g_conv_c8;
-extern int g_conv_xcd;
-extern int g_conv_x3;
-extern int g_conv_side_pre;
-extern int g_conv_pers, g_conv_pers_min_wgs, g_conv_pers_groups, g_conv_pers_nw, g_conv_wgrad_pers;
-extern int g_conv_wgrad_small;
-extern int g_conv_wgrad_groups;
-extern int g_conv_wgrad8_groups;
-extern int g_conv_wgrad8_gs;
-extern int g_conv_wgrad8_nch;
-extern int g_conv_cout1_d4;
-extern int g_conv_bf16_dp;
-extern int g_conv2d_s2_mfma;
-extern int g_conv2d_pp;
-extern int g_conv2d_wgrad_groups;
-extern int g_conv2d_wgrad_batch_groups;
-extern int g_conv_cout1_h4;
-static int g_sweep_bwd_variant = 0;   // knob "sweep_bwd": 0 = per-wave windows (<= 4 source views; the default), 1 = view-pair kernel with LDS atomics (what > 4 source views run).  (Round 3's projection-table form with an LDS-DMA ring measured 2.2x slower and was removed in round 4: DESIGN.md section 4, git tag r3-rejected-variants.)
-static int g_sweep_bwd_cpt = 4;       // knob "bwd_cpt": accepted and ignored (the 8-channels-per-thread form was measured slower and removed)
-static int g_sweep_bwd_pf = 0;        // knob "bwd_pf": 1 = block lookahead for 1-2 source views, 2 = ONE wave per SIMD for 3-4 source views
-static int g_sweep_xcd = 0;           // knob "sweep_xcd": XCD-compact workgroup order of the cached forward and the per-wave-window backward
-static int g_sweep_fwd_dl = 2;        // knob "fwd_dl": forward with LDS-staged per-plane depths (1), + all views' re-gathers in flight before the first sample (2, default since round 6: with the 4-wide tile -5.6 % at N = 3, -4.4 % at N = 5); 0: the round-1 loop
-static int g_sweep_bwd_gd = 2;        // knob "bwd_gd": 2 = upstream gradient requested two planes ahead at 2 waves/SIMD (1-2 source views), 0 = rotating set at 3 waves/SIMD
-static int g_sweep_fwd_pt = 0;        // knob "fwd_pt": the cached forward with the per-wave projection table (plane_sweep_variance_fwd_pt_kernel).  MEASURED AND REJECTED (round 6, profiles/r06_run15_*, r06_run16_*): 9-26 % fewer vector instructions per plane, bit-identical, and SLOWER at every view count -- N=3 0.108 -> 0.117 ms, N=5 0.208 -> 0.226, N=7 bf16 2.56 -> 2.95
-static int g_sweep_bwd_gd34 = 0;      // knob "bwd_gd34": 3-4 source views with the upstream gradient requested two planes ahead (as 1-2 views run), 2 waves/SIMD
-static int g_sweep_bwd_gpf = 0;       // knob "bwd_gpf": where the per-wave-window backward requests the next planes' upstream gradient: 0 top of the group, 1 after the plane's gathers
-int g_sweep_bwd_nowin = 0;            // knob "bwd_nowin" (tests): 1 = no LDS windows, every flush through global atomics
-int g_sweep_bwd_dslab = 0;            // knob "bwd_dslab": planes per workgroup of the per-wave-window backward, 0 = auto
-// Measurement knobs (A/B runs of tools/bench_kernels.py and the tests).  Full-string keys: an unknown or misspelt key
-// is an error, never a silent hit on another knob.  Process-wide; not part of the data path's contract.
-struct MvsKnob { const char* name; int* var; int lo, hi; };
-static const MvsKnob* mvs_find_knob(const char* key) {
-    static const MvsKnob knobs[] = {
-        {"nt", &g_sweep_nt, 0, 1},           {"tile_w", &g_sweep_tile_w, 0, 256},   {"dslab", &g_sweep_dslab, 0, 1 << 20},
-        {"conv_split", &g_conv_split, 0, 1}, {"conv_small", &g_conv_small, 0, 2}, {"conv_small_wgs", &g_conv_small_wgs, 0, 1 << 20}, {"tr2pw", &g_conv_tr2pw, 0, 1}, {"cc_wide", &g_conv_cc_wide, 0, 1}, {"cin1_vpt", &g_conv_cin1_vpt, 1, 5}, {"k8", &g_conv_c8, 0, 15},             {"cout1_d4", &g_conv_cout1_d4, 0, 3}, {"bf16_dp", &g_conv_bf16_dp, 0, 1}, {"conv2d_pp", &g_conv2d_pp, 0, 1},
-        {"wgrad2d_groups", &g_conv2d_wgrad_groups, 0, 1 << 20}, {"wgrad2d_batch", &g_conv2d_wgrad_batch_groups, 1, 4096},                     {"conv2d_s2_mfma", &g_conv2d_s2_mfma, 0, 2},
-        {"xcd", &g_conv_xcd, 0, 1}, {"side_pre", &g_conv_side_pre, 0, 1}, {"conv_pers", &g_conv_pers, 0, 1}, {"conv_pers_min", &g_conv_pers_min_wgs, 0, 1 << 30}, {"conv_pers_groups", &g_conv_pers_groups, 0, 4096}, {"conv_pers_nw", &g_conv_pers_nw, 4, 8}, {"wgrad_pers", &g_conv_wgrad_pers, 0, 1}, {"wgrad_small", &g_conv_wgrad_small, 0, 3}, {"wgrad_groups", &g_conv_wgrad_groups, 1, 768}, {"wgrad8_groups", &g_conv_wgrad8_groups, 1, 512}, {"wgrad8_gs", &g_conv_wgrad8_gs, 0, 2}, {"wgrad8_nch", &g_conv_wgrad8_nch, 1, 2}, {"cout1_h4", &g_conv_cout1_h4, 0, 1},          {"sweep_fwd", &g_sweep_fwd_variant, 0, 4}, {"sweep_bwd", &g_sweep_bwd_variant, 0, 1},
-        {"bwd_dslab", &g_sweep_bwd_dslab, 0, 1 << 20}, {"bwd_nowin", &g_sweep_bwd_nowin, 0, 1}, {"bwd_cpt", &g_sweep_bwd_cpt, 4, 8}, {"bwd_pf", &g_sweep_bwd_pf, 0, 2}, {"bwd_gd", &g_sweep_bwd_gd, 0, 2}, {"bwd_gd34", &g_sweep_bwd_gd34, 0, 1}, {"fwd_pt", &g_sweep_fwd_pt, 0, 1}, {"bwd_gpf", &g_sweep_bwd_gpf, 0, 1}, {"fwd_dl", &g_sweep_fwd_dl, 0, 2}, {"sweep_xcd", &g_sweep_xcd, 0, 1}, {"conv0_x3", &g_conv_x3, 0, 3},
-    };
-    for (const MvsKnob& k : knobs)
-        if (strcmp(key, k.name) == 0) return &k;
-    return nullptr;
-}
-extern "C" int mvs_set_tuning(const char* key, int value) {
-    MVS_REQUIRE(key, MVS_ERR_NULL, "mvs_set_tuning: null key");
-    const MvsKnob* k = mvs_find_knob(key);
-    if (!k) {
-        mvs_set_error("mvs_set_tuning: unknown key '%s'", key);
-        return MVS_ERR_UNSUPPORTED;
-    }
-    *k->var = value < k->lo ? k->lo : (value > k->hi ? k->hi : value);
-    return MVS_OK;
-}
-// the knob's current value (bench.py --ab restores the LIBRARY's defaults after a toggle: tests/test_capi_symbols.py holds
-// _lib.DEFAULT_TUNING against the values a freshly loaded library reports)
-extern "C" int mvs_get_tuning(const char* key, int* value) {
-    MVS_REQUIRE(key && value, MVS_ERR_NULL, "mvs_get_tuning: null argument");
-    const MvsKnob* k = mvs_find_knob(key);
-    if (!k) {
-        mvs_set_error("mvs_get_tuning: unknown key '%s'", key);
-        return MVS_ERR_UNSUPPORTED;
-    }
-    *value = *k->var;
-    return MVS_OK;
-}
+// Launchers.  Which variant runs is decided by the knobs of tuning.h (g_tune.sweep_fwd, fwd_dl, fwd_pt, sweep_bwd, bwd_*).  Measured:
+//  * fwd_dl = 2 is the default since round 6: with the 4-wide tile -5.6 % at N = 3, -4.4 % at N = 5.
+//  * fwd_pt (plane_sweep_variance_fwd_pt_kernel): MEASURED AND REJECTED (round 6, profiles/r06_run15_*, r06_run16_*): 9-26 % fewer
+//    vector instructions per plane, bit-identical, and SLOWER at every view count -- N=3 0.108 -> 0.117 ms, N=5 0.208 -> 0.226,
+//    N=7 bf16 2.56 -> 2.95
+//  * sweep_bwd: (Round 3's projection-table form with an LDS-DMA ring measured 2.2x slower and was removed in round 4: DESIGN.md
+//    section 4, git tag r3-rejected-variants.)
 
 // the projection-table forward serves a (C, views, channels per thread) combination when the (pixel, view) pairs of a wave fit its 64 lanes
 template <int C, int N, int CPT, bool BF>
@@ -1467,10 +1389,10 @@ static int launch_fwd(SweepArgs& a, hipStream_t st) {
     a.tiles_x = mvs_cdiv(a.W, Tile<C>::TW);
     a.tiles_y = mvs_cdiv(a.H, Tile<C>::TH);
     dim3 grid(a.tiles_x * a.tiles_y, mvs_cdiv(a.D, a.dslab), a.B), block(256);
-    const int variant = sweep_fwd_variant();
-    a.nt_store = g_sweep_nt;
-    a.xcd = g_sweep_xcd;
-    if (g_sweep_dslab > 0) a.dslab = g_sweep_dslab;
+    const int variant = g_tune.sweep_fwd;
+    a.nt_store = g_tune.nt;
+    a.xcd = g_tune.sweep_xcd;
+    if (g_tune.dslab > 0) a.dslab = g_tune.dslab;
     if (!a.warp_only && variant >= 2 && (a.NS <= 4 || a.NS == 6) && !(variant == 4 && a.NS > 2)) {
         constexpr int CPT8 = C >= 16 ? 8 : 4;
         constexpr int CPT16 = C >= 32 ? 16 : CPT8;
@@ -1483,13 +1405,13 @@ static int launch_fwd(SweepArgs& a, hipStream_t st) {
         //  config 2 0.1141 -> 0.1077 ms, at N = 5 0.2034 -> 0.1945, six interleaved rounds each: profiles/r06_run18_k1_knobs.log)
         //  Per-plane hypotheses at 32 channels only: with 16 channels (a 4 x 32 tile) and per-pixel hypotheses -- CVP's refine sweep at
         //  1152 x 864 -- the narrow tile costs 0.39 -> 0.43 ms and 1.02 -> 1.50 GB of traffic (profiles/r06_final_bench_c4.json vs r06_final5_*).
-        int tw = g_sweep_tile_w > 0 ? g_sweep_tile_w : (c16 ? TileC<C, CPT16>::TW : (c8 ? ((C == 32 && !a.per_pixel) ? 4 : TileC<C, CPT8>::TW) : TileC<C, 4>::TW));
+        int tw = g_tune.tile_w > 0 ? g_tune.tile_w : (c16 ? TileC<C, CPT16>::TW : (c8 ? ((C == 32 && !a.per_pixel) ? 4 : TileC<C, CPT8>::TW) : TileC<C, 4>::TW));
         if (tw > ppb) tw = ppb;
         while (ppb % tw) --tw;
         a.tile_w = tw;
         a.tiles_x = mvs_cdiv(a.W, tw);
         a.tiles_y = mvs_cdiv(a.H, ppb / tw);
-        if (g_sweep_dslab <= 0) {
+        if (g_tune.dslab <= 0) {
             // >= ~2500 workgroups, >= 8 planes each (rounds 1-5, 8 x 8 tiles: ~5000 workgroups, 12-16 planes:
             // profiles/r01_run16_k1_depth_slab_sweep.log); fewer, longer workgroups lose to load imbalance
             const long tiles = (long)a.tiles_x * a.tiles_y * a.B;
@@ -1498,7 +1420,7 @@ static int launch_fwd(SweepArgs& a, hipStream_t st) {
             while (slab > 8 && tiles * mvs_cdiv(a.D, slab) < 2500) slab = (slab + 1) / 2;
             a.dslab = slab;
         }
-        const int dl = a.per_pixel ? 0 : g_sweep_fwd_dl;   // knob "fwd_dl": 1 = LDS-staged depths, 2 = + in-block gather waits (per-plane hypotheses)
+        const int dl = a.per_pixel ? 0 : g_tune.fwd_dl;   // knob "fwd_dl": 1 = LDS-staged depths, 2 = + in-block gather waits (per-plane hypotheses)
         if (dl && a.dslab > 512) a.dslab = 512;
         dim3 gridc(a.tiles_x * a.tiles_y, mvs_cdiv(a.D, a.dslab), a.B);
         if (a.bf16_out) {
@@ -1512,12 +1434,12 @@ static int launch_fwd(SweepArgs& a, hipStream_t st) {
             const long tilesb = (long)a.tiles_x * a.tiles_y * a.B;
             int slab = a.D;
             while (slab > 8 && tilesb * mvs_cdiv(a.D, slab) < 5000) slab = (slab + 1) / 2;
-            a.dslab = g_sweep_dslab > 0 ? g_sweep_dslab : slab;
+            a.dslab = g_tune.dslab > 0 ? g_tune.dslab : slab;
             if (dl && a.dslab > 512) a.dslab = 512;
             dim3 gridb(a.tiles_x * a.tiles_y, mvs_cdiv(a.D, a.dslab), a.B);
 #define MVS_BF_CASE(N, CPTN)                                                                                                   \
     case N:                                                                                                                    \
-        if (dl && g_sweep_fwd_pt && launch_fwd_pt<CB, N, CPTN, true>(a, gridb, st)) {}                                         \
+        if (dl && g_tune.fwd_pt && launch_fwd_pt<CB, N, CPTN, true>(a, gridb, st)) {}                                         \
         else if (dl == 2) MVS_LAUNCH((plane_sweep_variance_fwd_cached_kernel<CB, N, CPTN, true, 2>), gridb, block, 0, st, a);  \
         else if (dl) MVS_LAUNCH((plane_sweep_variance_fwd_cached_kernel<CB, N, CPTN, true, 1>), gridb, block, 0, st, a);       \
         else MVS_LAUNCH((plane_sweep_variance_fwd_cached_kernel<CB, N, CPTN, true, 0>), gridb, block, 0, st, a);               \
@@ -1529,8 +1451,8 @@ static int launch_fwd(SweepArgs& a, hipStream_t st) {
 #define MVS_CACHED_CASE(N)                                                                                      \
     case N:                                                                                                     \
         if (c16) MVS_LAUNCH((plane_sweep_variance_fwd_cached_kernel<C, N, CPT16>), gridc, block, 0, st, a);    \
-        else if (c8 && dl && g_sweep_fwd_pt && launch_fwd_pt<C, N, CPT8, false>(a, gridc, st)) {}              \
-        else if (!c8 && dl && g_sweep_fwd_pt && launch_fwd_pt<C, N, 4, false>(a, gridc, st)) {}                \
+        else if (c8 && dl && g_tune.fwd_pt && launch_fwd_pt<C, N, CPT8, false>(a, gridc, st)) {}              \
+        else if (!c8 && dl && g_tune.fwd_pt && launch_fwd_pt<C, N, 4, false>(a, gridc, st)) {}                \
         else if (c8 && dl == 2) MVS_LAUNCH((plane_sweep_variance_fwd_cached_kernel<C, N, CPT8, false, 2>), gridc, block, 0, st, a); \
         else if (c8 && dl) MVS_LAUNCH((plane_sweep_variance_fwd_cached_kernel<C, N, CPT8, false, 1>), gridc, block, 0, st, a); \
         else if (c8) MVS_LAUNCH((plane_sweep_variance_fwd_cached_kernel<C, N, CPT8>), gridc, block, 0, st, a); \
@@ -1573,10 +1495,10 @@ static int launch_bwd_pw(SweepArgs& a, hipStream_t st) {
     int nslab = mvs_cdiv(1280, tiles);
     if (nslab > a.D / 16) nslab = a.D / 16;
     if (nslab < 1) nslab = 1;
-    a.dslab = g_sweep_bwd_dslab > 0 ? g_sweep_bwd_dslab : mvs_cdiv(a.D, nslab);
-    a.no_window = g_sweep_bwd_nowin;
-    a.gpf_late = g_sweep_bwd_gpf;
-    a.xcd = g_sweep_xcd;
+    a.dslab = g_tune.bwd_dslab > 0 ? g_tune.bwd_dslab : mvs_cdiv(a.D, nslab);
+    a.no_window = g_tune.bwd_nowin;
+    a.gpf_late = g_tune.bwd_gpf;
+    a.xcd = g_tune.sweep_xcd;
     dim3 grid(a.tiles_x * a.tiles_y, mvs_cdiv(a.D, a.dslab), a.B), block(256);
     if (a.warp_only) {
         if constexpr (NS_T == 1) MVS_LAUNCH((plane_sweep_variance_bwd_pw_kernel<C, 1, CPT, 2, GD, WPS, false, PFL>), grid, block, 0, st, a);
@@ -1588,18 +1510,18 @@ static int launch_bwd_pw(SweepArgs& a, hipStream_t st) {
 
 template <int C>
 static int launch_bwd(SweepArgs& a, hipStream_t st) {
-    if (g_sweep_bwd_variant != 1 && a.NS <= 4 && (long long)a.B * a.H * a.W * C < (1LL << 31)) {   // (32-bit feature-map offsets in the per-wave-window kernel)
+    if (g_tune.sweep_bwd != 1 && a.NS <= 4 && (long long)a.B * a.H * a.W * C < (1LL << 31)) {   // (32-bit feature-map offsets in the per-wave-window kernel)
         // 1-2 views: 2 waves per SIMD with the upstream gradient requested two planes ahead (knob "bwd_gd" = 0: 3 waves per SIMD, one
         // rotating register set); 3-4 views: 2 waves per SIMD (knob "bwd_pf" = 2: ONE wave per SIMD, 512 registers, nothing spills)
-        const bool gd2 = g_sweep_bwd_gd == 2;
-        if (g_sweep_bwd_pf == 1 && a.NS <= 2) {   // knob "bwd_pf" = 1: block lookahead (2 waves/SIMD, one-plane groups)
+        const bool gd2 = g_tune.bwd_gd == 2;
+        if (g_tune.bwd_pf == 1 && a.NS <= 2) {   // knob "bwd_pf" = 1: block lookahead (2 waves/SIMD, one-plane groups)
             if (a.NS == 1) return launch_bwd_pw<C, 1, 0, 2, true>(a, st);
             return launch_bwd_pw<C, 2, 0, 2, true>(a, st);
         }
         if (a.NS == 1) return gd2 ? launch_bwd_pw<C, 1, 2, 2>(a, st) : launch_bwd_pw<C, 1, 0, 3>(a, st);
         if (a.NS == 2) return gd2 ? launch_bwd_pw<C, 2, 2, 2>(a, st) : launch_bwd_pw<C, 2, 0, 3>(a, st);
-        if (a.NS == 3) return g_sweep_bwd_pf == 2 ? launch_bwd_pw<C, 3, 2, 1>(a, st) : (g_sweep_bwd_gd34 ? launch_bwd_pw<C, 3, 2, 2>(a, st) : launch_bwd_pw<C, 3, 0, 2>(a, st));
-        return g_sweep_bwd_pf == 2 ? launch_bwd_pw<C, 4, 2, 1>(a, st) : (g_sweep_bwd_gd34 ? launch_bwd_pw<C, 4, 2, 2>(a, st) : launch_bwd_pw<C, 4, 0, 2>(a, st));
+        if (a.NS == 3) return g_tune.bwd_pf == 2 ? launch_bwd_pw<C, 3, 2, 1>(a, st) : (g_tune.bwd_gd34 ? launch_bwd_pw<C, 3, 2, 2>(a, st) : launch_bwd_pw<C, 3, 0, 2>(a, st));
+        return g_tune.bwd_pf == 2 ? launch_bwd_pw<C, 4, 2, 1>(a, st) : (g_tune.bwd_gd34 ? launch_bwd_pw<C, 4, 2, 2>(a, st) : launch_bwd_pw<C, 4, 0, 2>(a, st));
     }
     // more than four source views (or knob "sweep_bwd" = 1): view pairs per workgroup, LDS-atomic windows
     a.tiles_x = mvs_cdiv(a.W, Tile<C>::TW);

@@ -14,10 +14,6 @@ import collections
 import torch
 import torch.nn.functional as F
 
-# every knob a case may set; restored from the compiled defaults (read through mvs_get_tuning before the first case)
-KNOBS = ("conv_pers", "conv_pers_min", "conv_pers_groups", "conv_pers_nw", "wgrad_pers", "wgrad_small", "wgrad_groups", "cout1_h4",
-         "cin1_vpt", "conv_small", "conv_small_wgs", "wgrad8_gs")
-
 Variant = collections.namedtuple("Variant", "name knobs trace")
 Case = collections.namedtuple("Case", "id op cin cout stride transposed dims epilogue variants base bitwise")
 
@@ -155,22 +151,6 @@ GENERIC_LABELS = ("conv_igemm", "conv_wgrad nbw", "conv_wgrad (small")     # wha
 
 def ids(cases):
     return [c.id for c in cases]
-
-
-def read_knobs(lib):
-    import ctypes as C
-    out = {}
-    for k in KNOBS:
-        v = C.c_int(-1)
-        lib.call("mvs_get_tuning", k.encode(), C.byref(v))
-        out[k] = v.value
-    return out
-
-
-def set_knobs(lib, defaults, knobs):
-    """every knob of KNOBS: the case's value, else the compiled default"""
-    for k in KNOBS:
-        lib.call("mvs_set_tuning", k.encode(), int(knobs.get(k, defaults[k])))
 
 
 def make_inputs(case, b=2):

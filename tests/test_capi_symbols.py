@@ -4,6 +4,8 @@ import re
 
 import pytest
 
+from emul_util import emul_lib  # noqa: F401
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -136,3 +138,36 @@ def test_default_tuning_table_matches_the_library():
     assert not bad, "library default != _lib.DEFAULT_TUNING: %r" % bad
     with pytest.raises(ValueError, match="unknown key"):
         lib.call("mvs_get_tuning", b"no_such_knob", C.byref(C.c_int()))
+
+
+def test_tuning_scope_restores_after_an_exception_and_nests_in_order(emul_lib):
+    """MvsLib.tuning puts back what it READ, also when the body raises; nested scopes unwind innermost first."""
+    before = emul_lib.get_tuning("bwd_gd"), emul_lib.get_tuning("bwd_dslab")
+    with pytest.raises(KeyError):
+        with emul_lib.tuning(bwd_gd=0, bwd_dslab=7):
+            assert (emul_lib.get_tuning("bwd_gd"), emul_lib.get_tuning("bwd_dslab")) == (0, 7)
+            raise KeyError("from the body")
+    assert (emul_lib.get_tuning("bwd_gd"), emul_lib.get_tuning("bwd_dslab")) == before
+    with emul_lib.tuning(bwd_dslab=5):
+        with emul_lib.tuning(bwd_dslab=9, bwd_gd=1):
+            assert (emul_lib.get_tuning("bwd_gd"), emul_lib.get_tuning("bwd_dslab")) == (1, 9)
+        assert (emul_lib.get_tuning("bwd_gd"), emul_lib.get_tuning("bwd_dslab")) == (before[0], 5)
+    assert (emul_lib.get_tuning("bwd_gd"), emul_lib.get_tuning("bwd_dslab")) == before
+
+
+def test_tuning_scope_with_an_unknown_key_changes_nothing(emul_lib):
+    before = emul_lib.get_tuning("conv_pers_min")
+    with pytest.raises(ValueError, match="unknown key"):
+        with emul_lib.tuning(conv_pers_min=0, zz_no_such_knob=1):
+            pytest.fail("the body must not run")
+    assert emul_lib.get_tuning("conv_pers_min") == before
+
+
+def test_every_row_of_the_knob_list_is_a_key_at_its_default(emul_lib):
+    """csrc/tuning.h against the library built from it: every row is a key, and (no test leaves a knob changed) holds its default;
+    _lib.DEFAULT_TUNING names rows of the list only."""
+    from mvs_amd import _lib
+    txt = open(os.path.join(ROOT, "self-supervised-mvs_amd", "csrc", "tuning.h")).read()
+    rows = {k: int(d) for k, d in re.findall(r"^\s*X\((\w+),\s*(-?\d+),", txt, flags=re.M)}
+    assert len(rows) >= 40 and set(_lib.DEFAULT_TUNING) <= set(rows)
+    assert {k: emul_lib.get_tuning(k) for k in rows} == rows

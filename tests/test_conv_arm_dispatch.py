@@ -35,16 +35,12 @@ def test_launch_trace_reports_and_clears(emul_lib):
 
 @pytest.mark.parametrize("case", K.ALL, ids=K.ids(K.ALL))
 def test_conv_arm_case_reaches_its_arm(emul_lib, dry_launch, case):
-    defaults = K.read_knobs(emul_lib)
     inp = K.make_inputs(case)
-    try:
-        for v in ([case.base] if case.base is not None else []) + list(case.variants):
-            K.set_knobs(emul_lib, defaults, v.knobs)
+    for v in ([case.base] if case.base is not None else []) + list(case.variants):
+        with emul_lib.tuning(**v.knobs):
             emul_lib.launch_trace()
             K.run(case, inp, emul_lib)
             assert emul_lib.launch_trace() == v.trace, "%s/%s" % (case.id, v.name)
-    finally:
-        K.set_knobs(emul_lib, defaults, {})
 
 
 def test_case_table_names_every_arm():

@@ -79,19 +79,12 @@ def test_plane_sweep_backward_long_segment(emul_lib, c, ns, d, gd):
     ref = torch.randn(b, c, h, w, generator=g, requires_grad=True)
     srcs = [torch.randn(b, c, h, w, generator=g, requires_grad=True) for _ in range(ns)]
     depth = (430 + 1.5 * torch.arange(d)).unsqueeze(0).repeat(b, 1)
-    emul_lib.call("mvs_set_tuning", b"sweep_bwd", 0)                   # the round-2 per-wave-window kernel (kept behind the knob)
-    emul_lib.call("mvs_set_tuning", b"bwd_gd", max(gd, 0))
-    emul_lib.call("mvs_set_tuning", b"bwd_pf", 1 if gd < 0 else 0)   # gd = -1: the block-lookahead form
-    emul_lib.call("mvs_set_tuning", b"bwd_dslab", d)
-    try:
+    # sweep_bwd: the round-2 per-wave-window kernel (kept behind the knob)
+    # bwd_pf: gd = -1: the block-lookahead form
+    with emul_lib.tuning(sweep_bwd=0, bwd_gd=max(gd, 0), bwd_pf=1 if gd < 0 else 0, bwd_dslab=d):
         var = ops.plane_sweep_variance(ref, srcs, rot, trans, depth)
         gup = torch.randn(var.shape, generator=g)
         var.backward(gup)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"sweep_bwd", 0)
-        emul_lib.call("mvs_set_tuning", b"bwd_gd", 2)
-        emul_lib.call("mvs_set_tuning", b"bwd_pf", 0)
-        emul_lib.call("mvs_set_tuning", b"bwd_dslab", 0)
     got = [ref.grad.clone()] + [s.grad.clone() for s in srcs]
     for t in [ref] + srcs:
         t.grad = None
@@ -117,19 +110,11 @@ def test_plane_sweep_backward_wide_depth_range(emul_lib, c, ns, step, hw, varian
     # variant 2 = the per-wave-window kernel with its windows switched off (every flush takes the global-atomic path),
     # variant 3 = ... in its 3-waves/SIMD form (one rotating register set for the upstream gradient), variant 4 = ... at ONE
     # wave/SIMD for 3-4 source views, variant 5 = ... with the block lookahead (1-2 source views)
-    emul_lib.call("mvs_set_tuning", b"sweep_bwd", 1 if variant == 1 else 0)
-    emul_lib.call("mvs_set_tuning", b"bwd_nowin", 1 if variant == 2 else 0)
-    emul_lib.call("mvs_set_tuning", b"bwd_gd", 0 if variant == 3 else 2)
-    emul_lib.call("mvs_set_tuning", b"bwd_pf", 2 if variant == 4 else (1 if variant == 5 else 0))
-    try:
+    with emul_lib.tuning(sweep_bwd=1 if variant == 1 else 0, bwd_nowin=1 if variant == 2 else 0, bwd_gd=0 if variant == 3 else 2,
+                        bwd_pf=2 if variant == 4 else (1 if variant == 5 else 0)):
         var = ops.plane_sweep_variance(ref, srcs, rot, trans, depth)
         gup = torch.randn(var.shape, generator=g)
         var.backward(gup)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"sweep_bwd", 0)
-        emul_lib.call("mvs_set_tuning", b"bwd_nowin", 0)
-        emul_lib.call("mvs_set_tuning", b"bwd_gd", 2)
-        emul_lib.call("mvs_set_tuning", b"bwd_pf", 0)
     got = [ref.grad.clone()] + [s.grad.clone() for s in srcs]
     for t in [ref] + srcs:
         t.grad = None
@@ -190,9 +175,8 @@ CONV_CASES = [
 @pytest.fixture(params=[0, 2], ids=["full_tiles", "quarter_tiles"])
 def conv_tiles(request, emul_lib):
     """The generic implicit-GEMM kernel's two workgroup tilings (knob "conv_small": the library picks by launch size)."""
-    emul_lib.call("mvs_set_tuning", b"conv_small", request.param)
-    yield request.param
-    emul_lib.call("mvs_set_tuning", b"conv_small", 1)
+    with emul_lib.tuning(conv_small=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("cin,cout,stride,transposed,dims", CONV_CASES)
@@ -299,14 +283,11 @@ def test_conv3d_dgrad_with_summand_and_batchnorm_backward_statistics(emul_lib, c
     invstd = torch.rsqrt(var + 1e-5)
     stats = torch.stack([mean, invstd, gamma * invstd, beta - mean * gamma * invstd]).contiguous()
     slots = torch.zeros((8, 2, cin), dtype=torch.float64)
-    emul_lib.call("mvs_set_tuning", b"side_pre", side_pre)
+    knobs = {"side_pre": side_pre}
     if cout == 1:      # the direct Cin == 1 kernel: one voxel per thread (side_pre = 1) and four (knob cin1_vpt = 5: always; measured slower on the GPU, off by default)
-        emul_lib.call("mvs_set_tuning", b"cin1_vpt", 1 if side_pre else 5)
-    try:
+        knobs["cin1_vpt"] = 1 if side_pre else 5
+    with emul_lib.tuning(**knobs):
         gx = ops.conv3d_dgrad(gy, w, x_shape, stride, transposed, add=add, bn=(raw.detach(), stats, slots))
-    finally:
-        emul_lib.call("mvs_set_tuning", b"side_pre", 1)
-        emul_lib.call("mvs_set_tuning", b"cin1_vpt", 1)
     assert float((gx - gtot).abs().max()) < 5e-4
     view = lambda v: v.view(1, cin, 1, 1, 1)
     dyh = gtot * (raw.detach() * view(stats[2]) + view(stats[3]) > 0)
@@ -379,15 +360,9 @@ def test_plane_sweep_fwd_depth_staging_forms_agree(emul_lib, c, ns):
     srcs = [torch.randn(b, c, h, w, generator=g) for _ in range(ns)]
     depth = (430 + 35.0 * torch.arange(d)).unsqueeze(0).repeat(b, 1)
     vols = []
-    try:
-        for dl, pt in ((0, 1), (1, 1), (2, 1), (1, 0)):     # fwd_pt = 1: the projection-table kernel serves dl != 0 (off by default: measured slower)
-            emul_lib.call("mvs_set_tuning", b"fwd_dl", dl)
-            emul_lib.call("mvs_set_tuning", b"fwd_pt", pt)
-            with torch.no_grad():
-                vols.append(ops.plane_sweep_variance(ref, srcs, rot, trans, depth).clone())
-    finally:
-        emul_lib.call("mvs_set_tuning", b"fwd_dl", 2)
-        emul_lib.call("mvs_set_tuning", b"fwd_pt", 0)
+    for dl, pt in ((0, 1), (1, 1), (2, 1), (1, 0)):     # fwd_pt = 1: the projection-table kernel serves dl != 0 (off by default: measured slower)
+        with emul_lib.tuning(fwd_dl=dl, fwd_pt=pt), torch.no_grad():
+            vols.append(ops.plane_sweep_variance(ref, srcs, rot, trans, depth).clone())
     exp = R.plane_sweep_variance(ref, srcs, [rot[:, i] for i in range(ns)], [trans[:, i] for i in range(ns)], depth)
     assert float((vols[1] - exp).abs().max()) < 2e-4
     assert torch.equal(vols[0], vols[1]) and torch.equal(vols[1], vols[2]) and torch.equal(vols[1], vols[3])
@@ -518,13 +493,10 @@ def test_conv0_input_gradient_split_bf16_form(emul_lib, b, dims, layout):
     else:     # ConvTranspose3d(8 -> 32, stride 1) forward: weight [Cin = 8][Cout = 32]
         ref = F.conv_transpose3d(gy.double(), w.double(), stride=1, padding=1)
         run = lambda: ops.conv3d_forward(gy, w, 1, True)[0]
-    try:
-        emul_lib.call("mvs_set_tuning", b"conv0_x3", 0)
+    with emul_lib.tuning(conv0_x3=0):
         base = run()
-        emul_lib.call("mvs_set_tuning", b"conv0_x3", 1)
+    with emul_lib.tuning(conv0_x3=1):
         got = run()
-    finally:
-        emul_lib.call("mvs_set_tuning", b"conv0_x3", 0)
     assert not torch.equal(base, got)                          # (the knob did select another kernel)
     e0 = (base.double() - ref).abs().sum() / ref.abs().sum()
     e1 = (got.double() - ref).abs().sum() / ref.abs().sum()
@@ -542,13 +514,10 @@ def test_conv0_forward_split_bf16_form(emul_lib, b, dims):
     w = torch.randn(8, 32, 3, 3, 3, generator=g) * 0.2
     x = torch.randn(b, 32, *dims, generator=g) * torch.rand(b, 32, *dims, generator=g).pow(4) * 10
     ref = F.conv3d(x.double(), w.double(), padding=1)
-    try:
-        emul_lib.call("mvs_set_tuning", b"conv0_x3", 0)
+    with emul_lib.tuning(conv0_x3=0):
         base, _ = ops.conv3d_forward(x, w, 1, False, want_stats=True)
-        emul_lib.call("mvs_set_tuning", b"conv0_x3", 2)
+    with emul_lib.tuning(conv0_x3=2):
         got, slots = ops.conv3d_forward(x, w, 1, False, want_stats=True)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"conv0_x3", 0)
     assert not torch.equal(base, got)
     e0 = (base.double() - ref).abs().sum() / ref.abs().sum()
     e1 = (got.double() - ref).abs().sum() / ref.abs().sum()
@@ -601,11 +570,8 @@ def test_plane_sweep_fwd_variants_agree(emul_lib, variant):
     ref = torch.randn(b, c, h, w, generator=g)
     srcs = [torch.randn(b, c, h, w, generator=g) for _ in range(ns)]
     depth = (430 + 25.0 * torch.arange(d)).unsqueeze(0)
-    emul_lib.call("mvs_set_tuning", b"sweep_fwd", variant)
-    try:
+    with emul_lib.tuning(sweep_fwd=variant):
         var = ops.plane_sweep_variance(ref, srcs, rot, trans, depth)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"sweep_fwd", 3)
     exp = R.plane_sweep_variance(ref, srcs, [rot[:, i] for i in range(ns)], [trans[:, i] for i in range(ns)], depth)
     assert float((var - exp).abs().max()) < 2e-4
 
@@ -615,8 +581,7 @@ def test_conv_multi_cout_tiles_per_workgroup(emul_lib):
     otherwise always take the split path."""
     from mvs_amd import ops
     g = torch.Generator().manual_seed(23)
-    emul_lib.call("mvs_set_tuning", b"conv_split", 0)
-    try:
+    with emul_lib.tuning(conv_split=0):
         for cin, cout, stride, transposed, dims in ((8, 32, 1, False, (4, 4, 16)), (16, 64, 1, False, (4, 4, 16)),
                                                     (32, 32, 2, True, (2, 4, 8))):
             x = torch.randn(1, cin, *dims, generator=g)
@@ -627,8 +592,6 @@ def test_conv_multi_cout_tiles_per_workgroup(emul_lib):
             y, parts = ops.conv3d_forward(x, w, stride, transposed, want_stats=True)
             assert float((y - yr).abs().max()) < 2e-4
             assert torch.allclose(parts.sum(0)[0].float(), yr.sum(dim=(0, 2, 3, 4)), atol=1e-2, rtol=1e-4)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"conv_split", 1)
 
 
 def test_bn_relu_2d(emul_lib):
@@ -711,9 +674,7 @@ def test_conv_c8_broadcast_operand_forward(emul_lib, cin, dims, xcd):
     x = torch.randn(2 if (cin == 8 and dims[2] == 33) else 1, cin, *dims, generator=g)   # (the emulated MFMA is a 64-thread barrier: keep the tile count small)
     w = torch.randn(8, cin, 3, 3, 3, generator=g) * 0.2
     yr = F.conv3d(x, w, padding=1)
-    emul_lib.call("mvs_set_tuning", b"k8", 7)
-    emul_lib.call("mvs_set_tuning", b"xcd", xcd)
-    try:
+    with emul_lib.tuning(k8=7, xcd=xcd):
         y, parts = ops.conv3d_forward(x, w, 1, False, want_stats=True)
         assert float((y - yr).abs().max()) < 2e-4
         s = parts.sum(0).float()
@@ -736,9 +697,6 @@ def test_conv_c8_broadcast_operand_forward(emul_lib, cin, dims, xcd):
             xr = x.clone().requires_grad_(True)
             F.conv3d(xr, w, padding=1).backward(yr)
             assert float((gx - xr.grad).abs().max()) < 2e-3
-    finally:
-        emul_lib.call("mvs_set_tuning", b"k8", 1)
-        emul_lib.call("mvs_set_tuning", b"xcd", 1)
 
 
 @pytest.mark.parametrize("name", ["g8_unsup_loss", "g8_unsup_loss_n4"])
@@ -867,21 +825,15 @@ def test_conv2d_family(emul_lib, cin, cout, ks, stride, hw):
     y2 = ops.conv2d_forward(x, w, None, stride)
     assert float((y2 - F.conv2d(x, w, None, stride=stride, padding=ks // 2)).abs().max()) < 2e-4
     if ks == 3 and min(cin, cout) <= 8:   # forward and / or input gradient above ran as pixel-pair GEMMs (knob conv2d_pp); here without
-        emul_lib.call("mvs_set_tuning", b"conv2d_pp", 0)
-        try:
+        with emul_lib.tuning(conv2d_pp=0):
             y0 = ops.conv2d_forward(x, w, b, stride)
             gx0 = ops.conv2d_dgrad(gy, w, tuple(x.shape), stride)
-        finally:
-            emul_lib.call("mvs_set_tuning", b"conv2d_pp", 1)
         assert float((y0 - yr).abs().max()) < 2e-4 and float((gx0 - xr.grad).abs().max()) < 3e-4
         assert float((y0 - y.detach()).abs().max()) < 2e-5      # same products, another summation order
     if stride == 2:   # the other forms of the stride-2 input gradient: direct VALU (0), four parity-class passes (1); default: ONE pass, compacted taps (2)
         for form in (0, 1):
-            emul_lib.call("mvs_set_tuning", b"conv2d_s2_mfma", form)
-            try:
+            with emul_lib.tuning(conv2d_s2_mfma=form):
                 gx = ops.conv2d_dgrad(gy, w, tuple(x.shape), 2)
-            finally:
-                emul_lib.call("mvs_set_tuning", b"conv2d_s2_mfma", 2)
             assert float((gx - xr.grad).abs().max()) < 3e-4, form
 
 
@@ -920,11 +872,8 @@ def test_conv2d_wgrad_persistent_workgroups_walk_several_tiles(emul_lib):
     gy = torch.randn(2, 16, 20, 70, generator=g).contiguous(memory_format=torch.channels_last)
     w = torch.zeros(16, 8, 3, 3, requires_grad=True)
     F.conv2d(x, w, padding=1).backward(gy)
-    emul_lib.call("mvs_set_tuning", b"wgrad2d_groups", 3)
-    try:
+    with emul_lib.tuning(wgrad2d_groups=3):
         gw = ops.conv2d_wgrad(x, gy, (16, 8, 3, 3), 1)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"wgrad2d_groups", 256)
     assert float((gw - w.grad).abs().max()) < 1e-3 * max(1.0, float(w.grad.abs().max()))
 
 
@@ -960,31 +909,22 @@ def test_conv3d_bf16_inference(emul_lib, cin, cout, stride, transposed, dims):
     assert float((y.float() - exp).abs().max()) <= 2 ** -7 * float(exp.abs().max()) + 1e-5
     assert float((yb - (ref + shift.view(1, -1, 1, 1, 1))).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
     if (cin, cout, stride) == (32, 8, 1):   # the default above is the depth-slice-pair form (knob bf16_dp); here one slice per MFMA
-        emul_lib.call("mvs_set_tuning", b"bf16_dp", 0)
-        try:
+        with emul_lib.tuning(bf16_dp=0):
             with torch.no_grad():
                 y1 = ops.conv3d_forward_bf16(x, wt, stride, transposed, scale=scale, shift=shift, skip=skip, relu=True)
-        finally:
-            emul_lib.call("mvs_set_tuning", b"bf16_dp", 1)
         assert float((y1.float() - exp).abs().max()) <= 2 ** -7 * float(exp.abs().max()) + 1e-5
         assert float((y1.float() - y.float()).abs().max()) <= 2 ** -7 * float(exp.abs().max())
     if transposed and cout == 8:   # the default above is the W-parity-merged form (knob tr2pw); here one MFMA per parity class
-        emul_lib.call("mvs_set_tuning", b"tr2pw", 0)
-        try:
+        with emul_lib.tuning(tr2pw=0):
             with torch.no_grad():
                 y8 = ops.conv3d_forward_bf16(x, wt, stride, transposed, scale=scale, shift=shift, skip=skip, relu=True)
-        finally:
-            emul_lib.call("mvs_set_tuning", b"tr2pw", 1)
         assert float((y8.float() - exp).abs().max()) <= 2 ** -7 * float(exp.abs().max()) + 1e-5
         assert float((y8.float() - y.float()).abs().max()) <= 2 ** -7 * float(exp.abs().max())
     if cout == 1:   # the default above is the direct four-outputs-per-thread form (knob cout1_d4, bit 1); here the MFMA form
-        emul_lib.call("mvs_set_tuning", b"cout1_d4", 0)
-        try:
+        with emul_lib.tuning(cout1_d4=0):
             with torch.no_grad():
                 y4 = ops.conv3d_forward_bf16(x, wt, stride, transposed, scale=scale, shift=shift, skip=skip, relu=True)
                 yb4 = ops.conv3d_forward_bf16(x, wt, stride, transposed, shift=shift, out_f32=True)
-        finally:
-            emul_lib.call("mvs_set_tuning", b"cout1_d4", 2)
         assert float((y4.float() - exp).abs().max()) <= 2 ** -7 * float(exp.abs().max()) + 1e-5
         assert float((yb4 - (ref + shift.view(1, -1, 1, 1, 1))).abs().max()) < 1e-4 * max(1.0, float(ref.abs().max()))
 
@@ -1261,21 +1201,15 @@ def test_plane_sweep_xcd_compact_order_and_merged_regather(emul_lib, ns, hw, d):
     depth = (430 + 21.0 * torch.arange(d)).unsqueeze(0).repeat(b, 1)
     gvar = torch.randn(b, c, d, h, w, generator=g)
     res = {}
-    try:
-        for key, knobs in (("base", {}), ("xcd", {b"sweep_xcd": 1}), ("both", {b"sweep_xcd": 1, b"fwd_dl": 2})):
-            emul_lib.call("mvs_set_tuning", b"sweep_xcd", knobs.get(b"sweep_xcd", 0))
-            emul_lib.call("mvs_set_tuning", b"fwd_dl", knobs.get(b"fwd_dl", 2))
-            emul_lib.call("mvs_set_tuning", b"dslab", 4)        # several slabs per tile: the slab index goes through the re-deal too
-            emul_lib.call("mvs_set_tuning", b"bwd_dslab", 4)
+    for key, knobs in (("base", {}), ("xcd", {"sweep_xcd": 1}), ("both", {"sweep_xcd": 1, "fwd_dl": 2})):
+        # dslab: several slabs per tile: the slab index goes through the re-deal too
+        with emul_lib.tuning(sweep_xcd=knobs.get("sweep_xcd", 0), fwd_dl=knobs.get("fwd_dl", 2), dslab=4, bwd_dslab=4):
             fr = [t.clone().requires_grad_(True) for t in [ref] + srcs]
             var = ops.plane_sweep_variance(fr[0], fr[1:], rot, trans, depth)
             grads = torch.autograd.grad(var, fr, gvar)
             with torch.no_grad():
                 v16 = ops.plane_sweep_variance(ref, srcs, rot, trans, depth, out_dtype=torch.bfloat16)
             res[key] = (var.detach(), v16, grads)
-    finally:
-        for k, v in ((b"sweep_xcd", 0), (b"fwd_dl", 2), (b"dslab", 0), (b"bwd_dslab", 0)):
-            emul_lib.call("mvs_set_tuning", k, v)
     for key in ("xcd", "both"):
         assert torch.equal(res[key][0], res["base"][0]), key
         assert torch.equal(res[key][1], res["base"][1]), key
@@ -1390,12 +1324,9 @@ def test_conv3d_wgrad_quarter_size_tiles(emul_lib, cin, cout, stride, transposed
     gy = torch.randn(yr.shape, generator=g)
     yr.backward(gy)
     outs = {}
-    try:
-        for mode in (0, 3):
-            emul_lib.call("mvs_set_tuning", b"wgrad_small", mode)
+    for mode in (0, 3):
+        with emul_lib.tuning(wgrad_small=mode):
             outs[mode] = ops.conv3d_wgrad(x, gy, wshape, stride, transposed)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"wgrad_small", 0)
     scale = max(1.0, float(wr.grad.abs().max()))
     assert float((outs[3] - wr.grad).abs().max()) < 1e-3 * scale
     assert float((outs[3] - outs[0]).abs().max()) < 2e-4 * scale
@@ -1595,12 +1526,11 @@ def test_conv2d_weight_gradients_of_all_layers_in_one_launch(emul_lib, budget, h
         xs.append(x); gys.append(gy); refs.append(w.grad); strides.append(stride)
         ws.append(w.detach().contiguous(memory_format=torch.channels_last) if wcl else w.detach())
     assert ops.conv2d_wgrad_batch_serves(xs, ws, strides)
-    emul_lib.call("mvs_set_tuning", b"wgrad2d_batch", budget)
-    ops._WGRAD_BATCH_PLANS.clear()
     try:
-        gws = ops.conv2d_wgrad_batch(xs, gys, ws, strides)
+        with emul_lib.tuning(wgrad2d_batch=budget):
+            ops._WGRAD_BATCH_PLANS.clear()
+            gws = ops.conv2d_wgrad_batch(xs, gys, ws, strides)
     finally:
-        emul_lib.call("mvs_set_tuning", b"wgrad2d_batch", 2048)
         ops._WGRAD_BATCH_PLANS.clear()
     for gw, ref, w, cfg in zip(gws, refs, ws, WGRAD_BATCH_LAYERS):
         assert gw.shape == ref.shape and gw.stride() == w.stride(), cfg
@@ -1623,14 +1553,9 @@ def test_conv_cout8_weight_gradient_two_chunks_per_workgroup(emul_lib, dims, xcd
     gy = torch.randn(y.shape, generator=g)
     y.backward(gy)
     outs = {}
-    emul_lib.call("mvs_set_tuning", b"xcd", xcd)
-    try:
-        for nch in (1, 2):
-            emul_lib.call("mvs_set_tuning", b"wgrad8_nch", nch)
+    for nch in (1, 2):
+        with emul_lib.tuning(xcd=xcd, wgrad8_nch=nch):
             outs[nch] = ops.conv3d_wgrad(x, gy, tuple(w.shape), 1, False)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"wgrad8_nch", 2)
-        emul_lib.call("mvs_set_tuning", b"xcd", 1)
     scale = max(1.0, float(w.grad.abs().max()))
     assert float((outs[2] - w.grad).abs().max()) < 1e-3 * scale
     assert float((outs[2] - outs[1]).abs().max()) < 2e-4 * scale
@@ -1680,21 +1605,13 @@ def test_conv3d_persistent_lds_dma_kernel_equals_one_tile_kernel(emul_lib, cin, 
     # the transposed geometry (conv11 forward, conv1's input gradient) reaches the persistent kernel only on full-size tiles: at these
     # sizes the auto tiling would pick GEOM_TR2_SMALL first and BOTH runs would take the one-tile kernel (the launch trace says so)
     tr2 = (stride == 2) and (transposed == (op == "fwd"))
-    emul_lib.call("mvs_set_tuning", b"conv_pers", 0)
-    emul_lib.call("mvs_set_tuning", b"conv_small", 0 if tr2 else 1)
-    try:
-        ref, ref_slots = run()
-        emul_lib.call("mvs_set_tuning", b"conv_pers", 1)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_min", 0)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_groups", groups)
-        emul_lib.launch_trace()
-        got, got_slots = run()
-        trace = emul_lib.launch_trace()
-    finally:
-        emul_lib.call("mvs_set_tuning", b"conv_pers", 1)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_min", 1024)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_groups", 0)
-        emul_lib.call("mvs_set_tuning", b"conv_small", 1)
+    with emul_lib.tuning(conv_small=0 if tr2 else 1):
+        with emul_lib.tuning(conv_pers=0):
+            ref, ref_slots = run()
+        with emul_lib.tuning(conv_pers=1, conv_pers_min=0, conv_pers_groups=groups):
+            emul_lib.launch_trace()
+            got, got_slots = run()
+            trace = emul_lib.launch_trace()
     assert trace == ["conv_pack_weights", "conv_pers nw=8"], trace
     assert torch.equal(got, ref), float((got - ref).abs().max())
     s_ref, s_got = ref_slots.sum(-3), got_slots.sum(-3)
@@ -1719,19 +1636,12 @@ def test_conv3d_persistent_weight_gradient(emul_lib, cin, cout, stride, transpos
     y = F.conv_transpose3d(x, w, stride=stride, padding=1, output_padding=stride - 1) if transposed else F.conv3d(x, w, stride=stride, padding=1)
     gy = torch.randn(y.shape, generator=g)
     y.backward(gy)
-    emul_lib.call("mvs_set_tuning", b"wgrad_pers", 0)
-    try:
+    with emul_lib.tuning(wgrad_pers=0):
         old = ops.conv3d_wgrad(x, gy, wshape, stride, transposed)
-        emul_lib.call("mvs_set_tuning", b"wgrad_pers", 1)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_min", 0)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_groups", groups)
+    with emul_lib.tuning(wgrad_pers=1, conv_pers_min=0, conv_pers_groups=groups):
         emul_lib.launch_trace()
         new = ops.conv3d_wgrad(x, gy, wshape, stride, transposed)
         assert emul_lib.launch_trace() == ["conv_wgrad_pers", "conv_wgrad_reduce narrow"]
-    finally:
-        emul_lib.call("mvs_set_tuning", b"wgrad_pers", 1)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_min", 1024)
-        emul_lib.call("mvs_set_tuning", b"conv_pers_groups", 0)
     scale = max(1.0, float(w.grad.abs().max()))
     assert float((new - w.grad).abs().max()) < 1e-3 * scale
     assert float((new - old).abs().max()) < 2e-4 * scale
@@ -1756,15 +1666,10 @@ def test_conv0_weight_gradient_output_gradient_shifted_form(emul_lib, waves, b, 
     y = F.conv3d(x, w, stride=1, padding=1)
     gy = torch.randn(y.shape, generator=g)
     y.backward(gy)
-    emul_lib.call("mvs_set_tuning", b"wgrad8_gs", 0)
-    try:
+    with emul_lib.tuning(wgrad8_gs=0):
         old = ops.conv3d_wgrad(x, gy, (8, 32, 3, 3, 3), 1, False)
-        emul_lib.call("mvs_set_tuning", b"wgrad8_gs", waves)
-        emul_lib.call("mvs_set_tuning", b"wgrad8_groups", groups)
+    with emul_lib.tuning(wgrad8_gs=waves, wgrad8_groups=groups):
         new = ops.conv3d_wgrad(x, gy, (8, 32, 3, 3, 3), 1, False)
-    finally:
-        emul_lib.call("mvs_set_tuning", b"wgrad8_gs", 2)
-        emul_lib.call("mvs_set_tuning", b"wgrad8_groups", 192)
     scale = max(1.0, float(w.grad.abs().max()))
     assert float((new - w.grad).abs().max()) < 1e-3 * scale
     assert float((new - old).abs().max()) < 2e-4 * scale

@@ -51,12 +51,10 @@ def dev():
 
 @pytest.fixture(scope="module")
 def knob_defaults(dev):
-    """the compiled defaults, read before any case sets a knob"""
+    """no test before this module left a knob changed (every case scopes its own: lib.tuning)"""
     from mvs_amd import _lib
-    d = K.read_knobs(_lib.get())
-    for k, v in d.items():
-        assert _lib.DEFAULT_TUNING.get(k, v) == v, "a test before this module left knob %s changed" % k
-    return d
+    for k, v in _lib.DEFAULT_TUNING.items():
+        assert _lib.get().get_tuning(k) == v, "a test before this module left knob %s changed" % k
 
 
 def _report(row):
@@ -90,23 +88,22 @@ def _check_stats(case, name, got, truth):
             "%s/%s statistic %d: %s vs %s" % (case.id, name, i, got[i].tolist(), truth[i].tolist())
 
 
-def _check_case(case, dev, defaults):
+def _check_case(case, dev):
     from mvs_amd import _lib
     lib = _lib.get()
     inp = K.make_inputs(case)
     t64, r32 = K.reference(case, inp, torch.float64), K.reference(case, inp, torch.float32)
     dinp = K.to_device(inp, dev)
     pers = any("pers" in lab for v in case.variants for lab in v.trace)
-    try:
-        base = None
-        if case.base is not None:
-            K.set_knobs(lib, defaults, case.base.knobs)
+    base = None
+    if case.base is not None:
+        with lib.tuning(**case.base.knobs):
             lib.launch_trace()
             base = K.run(case, dinp, lib)["out"].cpu()
             assert lib.launch_trace() == case.base.trace, case.id
-        for v in case.variants:
-            what = "%s/%s" % (case.id, v.name)
-            K.set_knobs(lib, defaults, v.knobs)
+    for v in case.variants:
+        what = "%s/%s" % (case.id, v.name)
+        with lib.tuning(**v.knobs):
             lib.launch_trace()
             first = K.run(case, dinp, lib)
             trace = lib.launch_trace()
@@ -136,8 +133,6 @@ def _check_case(case, dev, defaults):
             elif base is not None:
                 scale = max(1.0, float(t64["out"].abs().max()))
                 assert float((out - base).abs().max()) < 2e-4 * scale, what
-    finally:
-        K.set_knobs(lib, defaults, {})
 
 
 @pytest.mark.parametrize("case", K.PERS_FWD, ids=K.ids(K.PERS_FWD))
@@ -145,74 +140,74 @@ def test_conv_pers_forward(dev, knob_defaults, case):
     """conv_pers_kernel forward (label conv_pers), forced with conv_pers_min = 0, three persistent workgroups and one tile per
     workgroup; raw output + statistics, and scale / shift / ReLU / skip (the SIDE = 1 instantiation) + statistics; bitwise equal
     to the one-tile kernel (conv_igemm) it replaces."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.PERS_DGRAD, ids=K.ids(K.PERS_DGRAD))
 def test_conv_pers_input_gradient(dev, knob_defaults, case):
     """conv_pers_kernel as input gradient with summand and BatchNorm backward statistics (add=, bn=), through mvs_conv3d_dgrad
     (stride 1: flipped taps; stride 2: TR2_PW) and mvs_convT3d_dgrad (stride-2 geometry)."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.PERS_DEFAULT, ids=K.ids(K.PERS_DEFAULT))
 def test_conv_pers_default_dispatch(dev, knob_defaults, case):
     """No knob set: shapes ragged in D, H and W, large enough that the library itself takes conv_pers with at least three tiles
     for each of its 256 / 512 workgroups."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.PERS_NW4, ids=K.ids(K.PERS_NW4))
 def test_conv_pers_four_waves(dev, knob_defaults, case):
     """The four-wave instantiations of conv_pers_kernel (knob conv_pers_nw = 4; label conv_pers nw=4)."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.WGRAD_PERS, ids=K.ids(K.WGRAD_PERS))
 def test_conv_wgrad_pers(dev, knob_defaults, case):
     """conv_wgrad_pers_kernel (label conv_wgrad_pers) against fp64 autograd and against the register-staged conv_wgrad kernel it
     replaces (another split of the K sum: 2e-4 x scale, not bitwise)."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.WGRAD_SMALL, ids=K.ids(K.WGRAD_SMALL))
 def test_conv_wgrad_small_tiles(dev, knob_defaults, case):
     """conv_wgrad_kernel on the *_SMALL geometries (label conv_wgrad (small tiles)), one and two gradient-channel tiles."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.WGRAD_REDUCE, ids=K.ids(K.WGRAD_REDUCE))
 def test_conv_wgrad_reduce_wide_and_narrow(dev, knob_defaults, case):
     """conv_wgrad_reduce_wide_kernel (> 32 partial images) and conv_wgrad_reduce_kernel (label conv_wgrad_reduce wide / narrow)
     behind the same conv_wgrad launch."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.COUT1, ids=K.ids(K.COUT1))
 def test_conv_cout1_forms(dev, knob_defaults, case):
     """The Cout == 1 forward kernels with their bias (label conv_cout1 h4 / cin=8 / cin=16); ragged 4 x 8 x 32 and 4 x 4 x 16 tiles."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.CIN1, ids=K.ids(K.CIN1))
 def test_conv_cin1_input_gradient(dev, knob_defaults, case):
     """conv_cin1_kernel<C, 1> and <C, 4> (label conv_cin1 vpt=1 / vpt=4) with BatchNorm backward statistics; the last workgroup
     of either form is partly past the volume."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.AUTO, ids=K.ids(K.AUTO))
 def test_conv_auto_tiling(dev, knob_defaults, case):
     """conv_small = 1 (the library default): the trace says which tiling the generic kernel took (label conv_igemm s1 / s1_small /
     s2 / s2_small)."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 @pytest.mark.parametrize("case", K.C8_CG1, ids=K.ids(K.C8_CG1))
 def test_conv_c8_and_cg1_arms(dev, knob_defaults, case):
     """The Cout == 8 broadcast-operand forward (label conv_c8_fwd_bc), conv0's two weight-gradient forms (conv_c8_wgrad_gs,
     conv_c8_wgrad) and the Cout == 1 weight gradient (conv_wgrad_cg1): the trace ties each label to its kernel."""
-    _check_case(case, dev, knob_defaults)
+    _check_case(case, dev)
 
 
 # every launch label of csrc/conv3d.hip and csrc/conv3d_pers.hip

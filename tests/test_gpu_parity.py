@@ -120,20 +120,12 @@ def test_plane_sweep_backward_wide_depth_range(dev, c, ns, step, variant):
     # variant 2 = the per-wave-window kernel with its windows switched off (every flush takes the global-atomic path),
     # variant 3 = ... in its 3-waves/SIMD form (one rotating register set for the upstream gradient), variant 4 = ... at ONE
     # wave/SIMD for 3-4 source views, variant 5 = ... with the block lookahead (1-2 source views)
-    lib.call("mvs_set_tuning", b"sweep_bwd", 1 if variant == 1 else 0)
-    lib.call("mvs_set_tuning", b"bwd_nowin", 1 if variant == 2 else 0)
-    lib.call("mvs_set_tuning", b"bwd_gd", 0 if variant == 3 else 2)
-    lib.call("mvs_set_tuning", b"bwd_pf", 2 if variant == 4 else (1 if variant == 5 else 0))
-    try:
+    with lib.tuning(sweep_bwd=1 if variant == 1 else 0, bwd_nowin=1 if variant == 2 else 0, bwd_gd=0 if variant == 3 else 2,
+                   bwd_pf=2 if variant == 4 else (1 if variant == 5 else 0)):
         var = ops.plane_sweep_variance(refg, srcg, rot.to(dev), trans.to(dev), depth.to(dev))
         gup = torch.randn(var.shape, generator=g)
         var.backward(gup.to(dev))
         torch.cuda.synchronize()
-    finally:
-        lib.call("mvs_set_tuning", b"sweep_bwd", 0)
-        lib.call("mvs_set_tuning", b"bwd_nowin", 0)
-        lib.call("mvs_set_tuning", b"bwd_gd", 2)
-        lib.call("mvs_set_tuning", b"bwd_pf", 0)
     refc = ref.clone().requires_grad_(True)
     srcc = [s.clone().requires_grad_(True) for s in srcs]
     exp = R.plane_sweep_variance(refc, srcc, [rot[:, i] for i in range(ns)], [trans[:, i] for i in range(ns)], depth)
@@ -155,18 +147,11 @@ def test_plane_sweep_backward_long_segment(dev, c, ns, d, gd):
     depth = (430 + 1.5 * torch.arange(d)).unsqueeze(0).repeat(b, 1)
     refg = ref.to(dev).requires_grad_(True)
     srcg = [s.to(dev).requires_grad_(True) for s in srcs]
-    lib.call("mvs_set_tuning", b"bwd_gd", max(gd, 0))
-    lib.call("mvs_set_tuning", b"bwd_pf", 1 if gd < 0 else 0)   # gd = -1: the block-lookahead form
-    lib.call("mvs_set_tuning", b"bwd_dslab", d)
-    try:
+    with lib.tuning(bwd_gd=max(gd, 0), bwd_pf=1 if gd < 0 else 0, bwd_dslab=d):   # gd = -1: the block-lookahead form
         var = ops.plane_sweep_variance(refg, srcg, rot.to(dev), trans.to(dev), depth.to(dev))
         gup = torch.randn(var.shape, generator=g)
         var.backward(gup.to(dev))
         torch.cuda.synchronize()
-    finally:
-        lib.call("mvs_set_tuning", b"bwd_gd", 2)
-        lib.call("mvs_set_tuning", b"bwd_pf", 0)
-        lib.call("mvs_set_tuning", b"bwd_dslab", 0)
     refc = ref.clone().requires_grad_(True)
     srcc = [s.clone().requires_grad_(True) for s in srcs]
     exp = R.plane_sweep_variance(refc, srcc, [rot[:, i] for i in range(ns)], [trans[:, i] for i in range(ns)], depth)
@@ -188,16 +173,10 @@ def test_plane_sweep_fwd_depth_staging_forms_agree(dev, c, ns, d):
     srcs = [torch.randn(b, c, h, w, generator=g) for _ in range(ns)]
     depth = (430 + 9.0 * torch.arange(d)).unsqueeze(0).repeat(b, 1)
     vols = []
-    try:
-        # (round 6: knob fwd_pt = 1 sends fwd_dl != 0 to the projection-table kernel -- measured slower, off by default; the fourth volume is the cached kernel's dl = 1 form)
-        for dl, pt in ((0, 1), (1, 1), (2, 1), (1, 0)):
-            lib.call("mvs_set_tuning", b"fwd_dl", dl)
-            lib.call("mvs_set_tuning", b"fwd_pt", pt)
-            with torch.no_grad():
-                vols.append(ops.plane_sweep_variance(ref.to(dev), [s.to(dev) for s in srcs], rot.to(dev), trans.to(dev), depth.to(dev)).cpu())
-    finally:
-        lib.call("mvs_set_tuning", b"fwd_dl", 2)
-        lib.call("mvs_set_tuning", b"fwd_pt", 0)
+    # (round 6: knob fwd_pt = 1 sends fwd_dl != 0 to the projection-table kernel -- measured slower, off by default; the fourth volume is the cached kernel's dl = 1 form)
+    for dl, pt in ((0, 1), (1, 1), (2, 1), (1, 0)):
+        with lib.tuning(fwd_dl=dl, fwd_pt=pt), torch.no_grad():
+            vols.append(ops.plane_sweep_variance(ref.to(dev), [s.to(dev) for s in srcs], rot.to(dev), trans.to(dev), depth.to(dev)).cpu())
     exp = R.plane_sweep_variance(ref, srcs, [rot[:, i] for i in range(ns)], [trans[:, i] for i in range(ns)], depth)
     assert float((vols[1] - exp).abs().max()) < 2e-4
     assert torch.equal(vols[0], vols[1]) and torch.equal(vols[1], vols[2]) and torch.equal(vols[1], vols[3])
@@ -421,9 +400,8 @@ CONV_CASES = [
 def conv_tiles(request, dev):
     """The generic implicit-GEMM kernel's two workgroup tilings (knob "conv_small": the library picks by launch size)."""
     from mvs_amd import _lib
-    _lib.get().call("mvs_set_tuning", b"conv_small", request.param)
-    yield request.param
-    _lib.get().call("mvs_set_tuning", b"conv_small", 1)
+    with _lib.get().tuning(conv_small=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("cin,cout,stride,transposed,dims", CONV_CASES)
@@ -472,14 +450,9 @@ def test_conv0_weight_gradient_forms_vs_fp64_autograd(dev, b, dims, groups):
     w32 = torch.zeros(8, 32, 3, 3, 3, requires_grad=True)
     F.conv3d(x, w32, padding=1).backward(gy)
     got = {}
-    try:
-        for form in (2, 1, 0):
-            lib.call("mvs_set_tuning", b"wgrad8_gs", form)
-            lib.call("mvs_set_tuning", b"wgrad8_groups", groups)
+    for form in (2, 1, 0):
+        with lib.tuning(wgrad8_gs=form, wgrad8_groups=groups):
             got[form] = ops.conv3d_wgrad(x.to(dev), gy.to(dev), (8, 32, 3, 3, 3), 1, False).cpu()
-    finally:
-        lib.call("mvs_set_tuning", b"wgrad8_gs", _lib.DEFAULT_TUNING["wgrad8_gs"])
-        lib.call("mvs_set_tuning", b"wgrad8_groups", _lib.DEFAULT_TUNING["wgrad8_groups"])
     for form, gw in got.items():
         assert_grads_as_accurate_as_fp32_reference({"w": gw}, {"w": w32.grad}, {"w": w64.grad}, what="conv0 weight gradient, wgrad8_gs=%d" % form)
     scale = max(1.0, float(w64.grad.abs().max()))
@@ -495,12 +468,9 @@ def test_conv0_weight_gradient_forms_agree_at_config2_size(dev):
     x = (torch.randn(1, 32, 192, 128, 160, generator=g, device=dev) ** 2 * 0.3).contiguous(memory_format=torch.channels_last_3d)
     gy = (torch.randn(1, 8, 192, 128, 160, generator=g, device=dev) * 1e-3).contiguous(memory_format=torch.channels_last_3d)
     got = {}
-    try:
-        for form in (2, 1, 0):
-            lib.call("mvs_set_tuning", b"wgrad8_gs", form)
+    for form in (2, 1, 0):
+        with lib.tuning(wgrad8_gs=form):
             got[form] = ops.conv3d_wgrad(x, gy, (8, 32, 3, 3, 3), 1, False).double().cpu()
-    finally:
-        lib.call("mvs_set_tuning", b"wgrad8_gs", _lib.DEFAULT_TUNING["wgrad8_gs"])
     # truth of one (ci, co) plane of taps from an fp64 reduction on the GPU: dW[t][ci][co] = sum_p X[p + t - 1][ci] G[p][co]
     xs, gs = x[0, 5].double(), gy[0, 3].double()
     xp = F.pad(xs, (1, 1, 1, 1, 1, 1))
@@ -528,9 +498,7 @@ def test_conv_cout8_forms_and_tile_orders(dev, cin, dims, k8, xcd):
     gy = torch.randn(yr.shape, generator=g)
     yr.backward(gy)
     yr = yr.detach()
-    lib.call("mvs_set_tuning", b"k8", k8)
-    lib.call("mvs_set_tuning", b"xcd", xcd)
-    try:
+    with lib.tuning(k8=k8, xcd=xcd):
         y, parts = ops.conv3d_forward(x.to(dev), w.to(dev), 1, False, want_stats=True)
         assert float((y.cpu() - yr).abs().max()) < 3e-4
         s = parts.sum(0).float().cpu()
@@ -545,9 +513,6 @@ def test_conv_cout8_forms_and_tile_orders(dev, cin, dims, k8, xcd):
         assert float((y2.cpu() - ref2).abs().max()) < 5e-4
         gw = ops.conv3d_wgrad(x.to(dev), gy.to(dev), tuple(w.shape), 1, False)
         assert float((gw.cpu() - wr.grad).abs().max()) < 1e-3 * max(1.0, float(wr.grad.abs().max()))
-    finally:
-        lib.call("mvs_set_tuning", b"k8", _lib.DEFAULT_TUNING["k8"])
-        lib.call("mvs_set_tuning", b"xcd", _lib.DEFAULT_TUNING["xcd"])
 
 
 def _run_regnet_golden(dev, net, g, has_second, oracle_cls):
@@ -614,12 +579,9 @@ def test_conv3d_dgrad_with_summand_and_batchnorm_backward_statistics(dev, cin, c
     stats = torch.stack([mean, invstd, gamma * invstd, beta - mean * gamma * invstd]).contiguous()
     lib = _lib.get()
     slots = torch.zeros((lib.raw("mvs_bn_slots", cin), 2, cin), dtype=torch.float64, device=dev)
-    lib.call("mvs_set_tuning", b"side_pre", side_pre)
-    try:
+    with lib.tuning(side_pre=side_pre):
         gx = ops.conv3d_dgrad(gy.to(dev), w.to(dev), x_shape, stride, transposed, add=None if add is None else add.to(dev),
                               bn=(rawd.to(dev), stats.to(dev), slots))
-    finally:
-        lib.call("mvs_set_tuning", b"side_pre", 1)
     scale_g = max(1.0, float(gtot.abs().max()))
     assert float((gx.cpu() - gtot).abs().max()) < 5e-4 * scale_g
     view = lambda v: v.view(1, cin, 1, 1, 1)
@@ -805,12 +767,9 @@ def test_conv0_input_gradient_split_bf16_form_vs_fp64(dev, b, dims):
     gy = torch.randn(b, 8, *dims, generator=g) * torch.rand(b, 8, *dims, generator=g).pow(4) * 10
     ref = torch.nn.grad.conv3d_input((b, 32, *dims), w.double(), gy.double(), padding=1)
     got = {}
-    try:
-        for knob in (0, 1):
-            lib.call("mvs_set_tuning", b"conv0_x3", knob)
+    for knob in (0, 1):
+        with lib.tuning(conv0_x3=knob):
             got[knob] = ops.conv3d_dgrad(gy.to(dev), w.to(dev), (b, 32, *dims), 1, False).cpu().double()
-    finally:
-        lib.call("mvs_set_tuning", b"conv0_x3", 0)
     assert not torch.equal(got[0], got[1])
     e = {k: float((v - ref).abs().sum() / ref.abs().sum()) for k, v in got.items()}
     print("conv0 input gradient, relative L1 error against fp64: fp32 MFMA %.3e, split bf16 %.3e" % (e[0], e[1]))
@@ -829,13 +788,10 @@ def test_conv0_input_gradient_split_bf16_form_at_config2_size(dev):
     ga = torch.randn(1, 8, 192, 128, 160, generator=g).to(dev).contiguous(memory_format=torch.channels_last_3d)
     gb = torch.randn(1, 8, 192, 128, 160, generator=g).to(dev).contiguous(memory_format=torch.channels_last_3d)
     base = ops.conv3d_dgrad(ga, w, shape, 1, False)
-    try:
-        lib.call("mvs_set_tuning", b"conv0_x3", 1)
+    with lib.tuning(conv0_x3=1):
         xa = ops.conv3d_dgrad(ga, w, shape, 1, False)
         xb = ops.conv3d_dgrad(gb, w, shape, 1, False)
         xab = ops.conv3d_dgrad(2.0 * ga - 0.5 * gb, w, shape, 1, False)
-    finally:
-        lib.call("mvs_set_tuning", b"conv0_x3", 0)
     scale = float(base.abs().max())
     assert not torch.equal(base, xa)
     assert float((xa - base).abs().max()) < 2e-6 * scale and rel_l1(xa, base) < 1e-6
@@ -853,13 +809,10 @@ def test_conv0_forward_split_bf16_form_vs_fp64(dev, b, dims):
     x = torch.randn(b, 32, *dims, generator=g) * torch.rand(b, 32, *dims, generator=g).pow(4) * 10
     ref = F.conv3d(x.double(), w.double(), padding=1)
     got, stats = {}, {}
-    try:
-        for knob in (0, 2):
-            lib.call("mvs_set_tuning", b"conv0_x3", knob)
+    for knob in (0, 2):
+        with lib.tuning(conv0_x3=knob):
             y, slots = ops.conv3d_forward(x.to(dev), w.to(dev), 1, False, want_stats=True)
             got[knob], stats[knob] = y.cpu().double(), slots.sum(0).cpu()
-    finally:
-        lib.call("mvs_set_tuning", b"conv0_x3", 0)
     assert not torch.equal(got[0], got[2])
     e = {k: float((v - ref).abs().sum() / ref.abs().sum()) for k, v in got.items()}
     print("conv0 forward, relative L1 error against fp64: fp32 MFMA %.3e, split bf16 %.3e" % (e[0], e[2]))
@@ -879,13 +832,10 @@ def test_conv0_forward_split_bf16_form_at_config2_size(dev):
     xa = torch.randn(1, 32, 192, 128, 160, generator=g).to(dev).contiguous(memory_format=torch.channels_last_3d)
     xb = torch.randn(1, 32, 192, 128, 160, generator=g).to(dev).contiguous(memory_format=torch.channels_last_3d)
     base, s0 = ops.conv3d_forward(xa, w, 1, False, want_stats=True)
-    try:
-        lib.call("mvs_set_tuning", b"conv0_x3", 2)
+    with lib.tuning(conv0_x3=2):
         ya, s1 = ops.conv3d_forward(xa, w, 1, False, want_stats=True)
         yb, _ = ops.conv3d_forward(xb, w, 1, False)
         yab, _ = ops.conv3d_forward(2.0 * xa - 0.5 * xb, w, 1, False)
-    finally:
-        lib.call("mvs_set_tuning", b"conv0_x3", 0)
     scale = float(base.abs().max())
     assert not torch.equal(base, ya)
     assert float((ya - base).abs().max()) < 3e-6 * scale and rel_l1(ya, base) < 1e-6
@@ -900,11 +850,8 @@ def test_config2_train_step_with_split_bf16_conv0_input_gradient_vs_gpu_oracle(d
     gradient of conv0 as split-bf16 products): the same criteria."""
     from mvs_amd import _lib
     lib = _lib.get()
-    try:
-        lib.call("mvs_set_tuning", b"conv0_x3", 3)
+    with lib.tuning(conv0_x3=3):
         net, o, oracle, r, oracle64, t = _mvsnet_train_step_three_ways(dev, 3, 256, 320, 96, 1, torch.device("cpu"))
-    finally:
-        lib.call("mvs_set_tuning", b"conv0_x3", 0)
     assert rel_l1(o["depth"], r["depth"]) < 1e-3
     _check_param_grads(net, oracle, oracle64, ("prob.bias",), "MVSNet 256x320 D=96, conv0_x3=3")
 
@@ -1211,11 +1158,8 @@ def test_conv2d_family_vs_torch(dev, cin, cout, ks, stride, hw):
         from mvs_amd import _lib
         lib = _lib.get()
         for form in (1, 0):
-            lib.call("mvs_set_tuning", b"conv2d_s2_mfma", form)
-            try:
+            with lib.tuning(conv2d_s2_mfma=form):
                 gx = ops.conv2d_dgrad(gy.to(dev), w.to(dev), tuple(x.shape), 2)
-            finally:
-                lib.call("mvs_set_tuning", b"conv2d_s2_mfma", 2)
             assert float((gx.cpu() - xr.grad).abs().max()) < 5e-4, form
 
 

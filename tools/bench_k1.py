@@ -44,11 +44,8 @@ def main():
             timeit(run, 20)
             for rnd in range(6):
                 for name, knobs in variants:
-                    for k, v in knobs.items():
-                        lib.call("mvs_set_tuning", k.encode(), v)
-                    acc[name].append(timeit(run, 60, 3)[0])
-                    for k in knobs:
-                        lib.call("mvs_set_tuning", k.encode(), {"nt": 0, "dslab": 0, "tile_w": 0, "fwd_dl": 2}[k])
+                    with lib.tuning(**knobs):
+                        acc[name].append(timeit(run, 60, 3)[0])
         for name, _ in variants:
             v = sorted(acc[name])
             print("%-28s median of 6 medians %.4f ms (%.4f .. %.4f) = %.3f of 8 TB/s" % (name, v[len(v) // 2], v[0], v[-1], nbytes / v[len(v) // 2] / 1e6 / 8000), flush=True)
@@ -57,12 +54,9 @@ def main():
             [("tile_w=%d" % t, {"tile_w": t}) for t in (4, 8, 16, 32)] + [("fwd_dl=%d" % d, {"fwd_dl": d}) for d in (0, 2)] + [("default again", {})]
     with torch.no_grad():
         for name, knobs in cases:
-            for k, v in knobs.items():
-                lib.call("mvs_set_tuning", k.encode(), v)
-            med, mn = timeit(run)
+            with lib.tuning(**knobs):
+                med, mn = timeit(run)
             print("%-16s %.4f ms (min %.4f)  %.1f GB/s = %.3f of 8 TB/s" % (name, med, mn, nbytes / med / 1e6, nbytes / med / 1e6 / 8000), flush=True)
-            for k in knobs:
-                lib.call("mvs_set_tuning", k.encode(), {"nt": 0, "dslab": 0, "tile_w": 0, "fwd_dl": 2}[k])
 
 if __name__ == "__main__":
     main()

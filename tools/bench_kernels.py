@@ -67,11 +67,8 @@ def main():
     skip_sweep = bool(os.environ.get("MVS_BENCH_SKIP_SWEEP"))
     with torch.no_grad():
         for variant, label in (((3, "cached8"),) if skip_sweep else ((0, "direct"), (2, "cached4"), (3, "cached8"), (4, "cached16"))):
-            lib.call("mvs_set_tuning", b"sweep_fwd", variant)
-            add("sweep_fwd[%s]" % label, lambda: ops.plane_sweep_variance(feats[0], feats[1:], rot, trans, depth), "hbm", k1_bytes)
-        lib.call("mvs_set_tuning", b"dslab", 0)
-        lib.call("mvs_set_tuning", b"tile_w", 0)
-        lib.call("mvs_set_tuning", b"sweep_fwd", 3)
+            with lib.tuning(sweep_fwd=variant):
+                add("sweep_fwd[%s]" % label, lambda: ops.plane_sweep_variance(feats[0], feats[1:], rot, trans, depth), "hbm", k1_bytes)
         var = ops.plane_sweep_variance(feats[0], feats[1:], rot, trans, depth)
         add("calibration: fill_ 503 MB (write only)", lambda: var.fill_(1.0), "hbm", C * vox * 4)
         tmp = torch.empty_like(var)
@@ -94,18 +91,11 @@ def main():
         gv5 = torch.randn_like(v5)
         nbytes = C * vox * 4 + 2 * (ns_ + 1) * C * H * W * 4
         for variant, gd, pf, dslab in ((1, 2, 0, 0), (0, 0, 0, 0), (0, 2, 0, 0)):
-            lib.call("mvs_set_tuning", b"sweep_bwd", variant)
-            lib.call("mvs_set_tuning", b"bwd_dslab", dslab)
-            lib.call("mvs_set_tuning", b"bwd_gd", gd)
-            lib.call("mvs_set_tuning", b"bwd_pf", pf)
-            add("sweep_bwd N=%d [%s%s]%s" % (ns_ + 1, "round-2 per-wave windows, %s%s" % ("gradient 2 planes ahead" if gd == 2 else "rotating gradient set",
-                                                                                   ", 1 wave/SIMD (3-4 views)" if pf == 2 else "") if variant == 0
-                                             else "round-1 view pairs + LDS atomics", ", dslab %d" % dslab if dslab else "", label),
-                lambda: torch.autograd.grad(v5, f5, gv5, retain_graph=True), "hbm", nbytes)
-        lib.call("mvs_set_tuning", b"sweep_bwd", _lib.DEFAULT_TUNING.get("sweep_bwd", 0))
-        lib.call("mvs_set_tuning", b"bwd_dslab", 0)
-        lib.call("mvs_set_tuning", b"bwd_gd", 2)
-        lib.call("mvs_set_tuning", b"bwd_pf", 0)
+            with lib.tuning(sweep_bwd=variant, bwd_dslab=dslab, bwd_gd=gd, bwd_pf=pf):
+                add("sweep_bwd N=%d [%s%s]%s" % (ns_ + 1, "round-2 per-wave windows, %s%s" % ("gradient 2 planes ahead" if gd == 2 else "rotating gradient set",
+                                                                                       ", 1 wave/SIMD (3-4 views)" if pf == 2 else "") if variant == 0
+                                                 else "round-1 view pairs + LDS atomics", ", dslab %d" % dslab if dslab else "", label),
+                    lambda: torch.autograd.grad(v5, f5, gv5, retain_graph=True), "hbm", nbytes)
 
     if not skip_sweep:
         sweep_bwd_case(NS, "")
@@ -119,12 +109,9 @@ def main():
         y0, _ = ops.conv3d_forward(var, w0, 1, False)
         gy0 = torch.randn_like(y0)
         for k8, xcd, label in ((0, 1, "16x16x4 padded"), (7, 0, "4x4x1 broadcast operand, linear"), (7, 1, "4x4x1 broadcast operand, XCD bricks")):
-            lib.call("mvs_set_tuning", b"k8", k8)
-            lib.call("mvs_set_tuning", b"xcd", xcd)
-            add("conv0 fwd 32>8 [%s]" % label, lambda: ops.conv3d_forward(var, w0, 1, False, want_stats=True), "mfma", fl0)
-            add("conv0 wgrad [%s]" % label, lambda: ops.conv3d_wgrad(var, gy0, tuple(w0.shape), 1, False), "mfma", fl0)
-        lib.call("mvs_set_tuning", b"k8", _lib.DEFAULT_TUNING["k8"])
-        lib.call("mvs_set_tuning", b"xcd", _lib.DEFAULT_TUNING["xcd"])
+            with lib.tuning(k8=k8, xcd=xcd):
+                add("conv0 fwd 32>8 [%s]" % label, lambda: ops.conv3d_forward(var, w0, 1, False, want_stats=True), "mfma", fl0)
+                add("conv0 wgrad [%s]" % label, lambda: ops.conv3d_wgrad(var, gy0, tuple(w0.shape), 1, False), "mfma", fl0)
         add("conv0 dgrad", lambda: ops.conv3d_dgrad(gy0, w0, tuple(var.shape), 1, False), "mfma", fl0)
         # L0 8-channel layers
         w1 = (torch.randn(16, 8, 3, 3, 3, generator=g) * 0.05).to(dev)

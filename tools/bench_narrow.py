@@ -65,19 +65,13 @@ def main():
     only = os.environ.get("MVS_NARROW_ONLY", "")
     with torch.no_grad():
         for st in settings:
-            pairs = [kv.split("=") for kv in st.split(",") if kv]
-            for k, v in pairs:
-                lib.call("mvs_set_tuning", k.encode(), int(v))
             print("---- %s" % (st or "defaults"), flush=True)
-            for name, fn, nbytes in cases:
-                if only and only not in name:
-                    continue
-                med, mn = timeit(fn)
-                print("%-34s %7.3f ms (min %6.3f)   floor %5.3f ms   %4.1f%% of HBM peak" % (name, med, mn, nbytes / 8e12 * 1e3, 100 * nbytes / 8e12 * 1e3 / med), flush=True)
-            for k, v in pairs:
-                dflt = _lib.DEFAULT_TUNING.get(k)
-                if dflt is not None:
-                    lib.call("mvs_set_tuning", k.encode(), dflt)
+            with lib.tuning(**{k: int(v) for k, v in (kv.split("=") for kv in st.split(",") if kv)}):
+                for name, fn, nbytes in cases:
+                    if only and only not in name:
+                        continue
+                    med, mn = timeit(fn)
+                    print("%-34s %7.3f ms (min %6.3f)   floor %5.3f ms   %4.1f%% of HBM peak" % (name, med, mn, nbytes / 8e12 * 1e3, 100 * nbytes / 8e12 * 1e3 / med), flush=True)
 
 
 if __name__ == "__main__":

@@ -54,12 +54,9 @@ for _ in range(3):
             w0 = (torch.randn(8, 32, 3, 3, 3, generator=g) * 0.05).to(dev)
             if os.environ.get("MVS_PMC_VARIANTS"):   # A/B of the Cout==8 kernel forms / tile orders (per-dispatch order in the summary)
                 for k8, xcd in ((1, 0), (1, 1), (7, 0), (7, 1)):
-                    lib.call("mvs_set_tuning", b"k8", k8)
-                    lib.call("mvs_set_tuning", b"xcd", xcd)
-                    y0, _ = ops.conv3d_forward(v, w0, 1, False, want_stats=True)
-                    ops.conv3d_wgrad(v, y0, tuple(w0.shape), 1, False)
-                lib.call("mvs_set_tuning", b"k8", 7)
-                lib.call("mvs_set_tuning", b"xcd", 1)
+                    with lib.tuning(k8=k8, xcd=xcd):
+                        y0, _ = ops.conv3d_forward(v, w0, 1, False, want_stats=True)
+                        ops.conv3d_wgrad(v, y0, tuple(w0.shape), 1, False)
             y0, _ = ops.conv3d_forward(v, w0, 1, False, want_stats=True)
             ops.conv3d_wgrad(v, y0, tuple(w0.shape), 1, False)
             ops.conv3d_dgrad(y0, w0, tuple(v.shape), 1, False)
