@@ -425,6 +425,39 @@ int mvs_feature_bwd(int n, const MvsFeatBlock* blocks, int N, int G, const float
                     float* dgrad_ws, float* const* gw, float* wgrad_ws_main, float* wgrad_ws_side, float* const* dgamma,
                     float* const* dbeta, int early_from, hipStream_t main_stream, hipStream_t side_stream, int* side_stream_used);
 
+/* ---- Wide forward 2-D convolutions: the frozen VGG-style trunk in front of the NMF (csrc/conv2d_wide_kernels.h) -----------------
+ * 3x3, stride 1, pad 1, fp32, forward only, channels-last images x [N,H,W,Cin] -> y [N,H,W,Cout]; Cin = 3 or 32..512 and
+ * Cout = 32..512 in steps of 32 (the existing mvs_conv2d_* family serves 1..32 or exactly 64 channels).  Implicit GEMM on the
+ * 16x16x4 fp32 MFMA over flattened positions; which tile / split-K arm ran is in mvs_launch_trace ("conv2d_wide cin3",
+ * "conv2d_wide t128x64", "conv2d_wide t64x64", "conv2d_wide splitk=N" + "conv2d_wide reduce", "pool2x2", "resize_cl").  No
+ * atomics: two calls give the same bits.  All pointers 16-byte aligned.
+ * mvs_conv2d_wide_packed_floats(Cin, Cout): floats of a layer's weight image; mvs_conv2d_wide_pack_weights fills it from the parameter
+ *   w [Cout][Cin][3][3] (w_channels_last: [Cout][3][3][Cin] in memory), read in place.  Pack once per weight version.
+ * mvs_conv2d_wide_workspace_floats(N, H, W, Cin, Cout): floats of the `ws` of mvs_conv2d_wide_fwd for this layer (the
+ *   full-resolution image in front of a pool and the partial images of a split-K launch); -1 outside the served set.
+ * mvs_conv2d_wide_fwd: y = [relu](conv(x) + bias), bias may be NULL; pool: followed by a 2x2 stride-2 max pool (floor on odd sizes),
+ *   y is then [N,H/2,W/2,Cout].  ws may be NULL when neither a pool nor a split-K launch needs it.
+ * mvs_maxpool2x2_cl: x [N,H,W,C] -> y [N,H/2,W/2,C], C a multiple of 4.
+ * mvs_resize_bilinear_cl: x [N,C,H,W] (contiguous) -> y [N,oh,ow,C] by the rule of bilinear interpolation with align_corners = False
+ *   (source coordinate max(0, (o + 0.5) * in / out - 0.5)): the resize and the layout change in front of the trunk in one pass.
+ * mvs_conv_trunk_fwd: n layers as ONE call -- layer i reads x (i = 0) or the previous output and writes buf_a / buf_b in turn, the last
+ *   layer writes out [N,h,w,Cout_last]; packed[i] / bias[i] (NULL entries allowed in bias) per layer; buf_a, buf_b: each the largest
+ *   output of layers 0 .. n-2; ws: the largest mvs_conv2d_wide_workspace_floats of the chain.  The same kernels in the same order
+ *   as n mvs_conv2d_wide_fwd calls; every layer is checked before the first launch. */
+#define MVS_TRUNK_MAX_LAYERS 32
+typedef struct MvsTrunkLayer {
+    int cin, cout, relu, pool_after;
+} MvsTrunkLayer;
+long long mvs_conv2d_wide_workspace_floats(int N, int H, int W, int Cin, int Cout);
+long long mvs_conv2d_wide_packed_floats(int Cin, int Cout);
+int mvs_conv2d_wide_pack_weights(const float* w, float* ws, int Cin, int Cout, int w_channels_last, hipStream_t stream);
+int mvs_conv2d_wide_fwd(const float* x, const float* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin,
+                        int Cout, int relu, int pool, hipStream_t stream);
+int mvs_maxpool2x2_cl(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream);
+int mvs_resize_bilinear_cl(const float* x, float* y, int N, int C, int H, int W, int oh, int ow, hipStream_t stream);
+int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const float* const* packed, const float* const* bias, const float* x,
+                       float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, hipStream_t stream);
+
 /* ---- geometric-consistency filter on the path's depth maps ---------------------------------------------
  * Replaces reproject_with_depth + check_geometric_consistency (jdacs/eval.py:169-224) for ALL source views of one
  * reference view, and the accumulation of filter_depth (eval.py:372-385): per pixel and source view, project with the

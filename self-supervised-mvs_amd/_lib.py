@@ -29,6 +29,11 @@ class MvsFeatBlock(C.Structure):
                 ("h", _i), ("w", _i)]
 
 
+class MvsTrunkLayer(C.Structure):
+    """include/mvs_hip.h: one 3x3 convolution (+ ReLU, + 2x2 max pool) of a frozen trunk (mvs_conv_trunk_fwd)"""
+    _fields_ = [("cin", _i), ("cout", _i), ("relu", _i), ("pool_after", _i)]
+
+
 _pp = C.POINTER(C.c_void_p)   # array of device pointers
 
 # name -> (restype, argtypes); every symbol include/mvs_hip.h declares
@@ -111,6 +116,13 @@ SIGNATURES = {
     "mvs_seg_loss_workspace_floats": (_ll, [_i, _i, _i, _i, _i]),
     "mvs_seg_loss_fwd": (_i, [_f, C.POINTER(C.c_void_p), _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _s]),
     "mvs_seg_loss_bwd": (_i, [_f, C.POINTER(C.c_void_p), _f, _f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _s]),
+    "mvs_conv2d_wide_workspace_floats": (_ll, [_i] * 5),
+    "mvs_conv2d_wide_packed_floats": (_ll, [_i, _i]),
+    "mvs_conv2d_wide_pack_weights": (_i, [_f, _f, _i, _i, _i, _s]),
+    "mvs_conv2d_wide_fwd": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _s]),
+    "mvs_maxpool2x2_cl": (_i, [_f, _f, _i, _i, _i, _i, _s]),
+    "mvs_resize_bilinear_cl": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
+    "mvs_conv_trunk_fwd": (_i, [_i, C.POINTER(MvsTrunkLayer), _pp, _pp, _f, _f, _f, _f, _f, _i, _i, _i, _s]),
 }
 
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_CONVT_FWD, OP_CONVT_DGRAD, OP_CONVT_WGRAD = range(6)

@@ -884,6 +884,8 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_batch_reduce_kernel(Wg2Batch
     }
 }
 
+#include "conv2d_wide_kernels.h"   // the wide forward family of the frozen VGG-style trunk (host side: end of this file)
+
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
@@ -1336,4 +1338,176 @@ extern "C" int mvs_conv2d_wgrad_batch_xf(int n, const float* const* x, const flo
                                          const float* const* gy, float* const* gw, float* ws, const int* shapes, hipStream_t stream) {
     MVS_REQUIRE(x_stats, MVS_ERR_NULL, "conv2d_wgrad_batch_xf: null pointer argument");
     return wg2_run(n, x, x_stats, imgs_per_group, gy, gw, ws, shapes, stream);
+}
+
+// ---- wide forward family (conv2d_wide_kernels.h): 3 or 32..512 -> 32..512 channels in steps of 32, 3x3 stride 1 pad 1 ----------
+static bool c2w_served(int Cin, int Cout) {
+    return (Cin == 3 || (Cin >= 32 && Cin <= 512 && Cin % 32 == 0)) && Cout >= 32 && Cout <= 512 && Cout % 32 == 0;
+}
+static long long c2w_packed_floats(int Cin, int Cout) { return (long long)c2w_nsteps(Cin) * 2 * c2w_nbp(Cout) * 256; }
+
+// Which kernel a layer runs (knobs c2w_*, csrc/tuning.h; measured on the VGG19 trunk at seven 224x224 images).
+// t128x64 from two workgroups per CU on (688 workgroups at 56x56: 0.277 ms against t64x64's 0.322 for 256 -> 256; 344 at 28x28:
+// 0.371 against 0.300 for 512 -> 512); under that t64x64; and where even t64x64 leaves CUs without a workgroup (512 -> 512 at
+// 14x14: 176 workgroups of 144 k-steps) K is split until the launch has c2w_split_min workgroups, as long as every range keeps
+// at least nine steps (one chunk of 32 input channels): 0.133 ms unsplit, 0.120 / 0.091 / 0.098 with 2 / 4 / 8 ranges.
+struct C2wPlan { int mb, split; };
+static C2wPlan c2w_plan(long long M, int Cin, int Cout) {
+    const int nsteps = c2w_nsteps(Cin);
+    const long long ct = c2w_nbp(Cout) / 4, wg128 = (M + 127) / 128 * ct, wg64 = (M + 63) / 64 * ct;
+    C2wPlan p = {2, 1};
+    if (Cin == 3) { p.mb = 4; return p; }
+    if (g_tune.c2w_tile == 2 || (g_tune.c2w_tile == 0 && wg128 >= g_tune.c2w_big_min)) p.mb = 4;
+    int split = g_tune.c2w_splitk;
+    if (split == 0) {
+        split = 1;
+        if (p.mb == 2)
+            while (wg64 * split < g_tune.c2w_split_min && split < 8 && nsteps / (2 * split) >= 9) split *= 2;
+    }
+    p.split = split < 1 ? 1 : (split > nsteps ? nsteps : split);
+    return p;
+}
+
+static int c2w_check(const char* what, int N, int H, int W, int Cin, int Cout) {
+    MVS_REQUIRE(N > 0 && H > 0 && W > 0 && (long long)N * H * W < (1LL << 31) - 256, MVS_ERR_SHAPE, "%s: bad shape N=%d H=%d W=%d", what, N, H, W);
+    MVS_REQUIRE(c2w_served(Cin, Cout), MVS_ERR_UNSUPPORTED,
+                "%s: serves 3 or 32..512 input and 32..512 output channels in steps of 32, got %d -> %d", what, Cin, Cout);
+    return MVS_OK;
+}
+
+// floats of the `ws` argument of mvs_conv2d_wide_fwd: the full-resolution image in front of a pool, plus the partial images of a
+// split-K launch (the knobs are read now: query right before the call); -1 outside the served set
+extern "C" long long mvs_conv2d_wide_workspace_floats(int N, int H, int W, int Cin, int Cout) {
+    if (N <= 0 || H <= 0 || W <= 0 || (long long)N * H * W >= (1LL << 31) - 256 || !c2w_served(Cin, Cout)) return -1;
+    const long long M = (long long)N * H * W;
+    const C2wPlan p = c2w_plan(M, Cin, Cout);
+    return M * Cout * (1 + (p.split > 1 ? p.split : 0));
+}
+extern "C" long long mvs_conv2d_wide_packed_floats(int Cin, int Cout) { return c2w_served(Cin, Cout) ? c2w_packed_floats(Cin, Cout) : -1; }
+
+extern "C" int mvs_conv2d_wide_pack_weights(const float* w, float* ws, int Cin, int Cout, int w_channels_last, hipStream_t stream) {
+    MVS_REQUIRE(c2w_served(Cin, Cout), MVS_ERR_UNSUPPORTED,
+                "conv2d_wide_pack_weights: serves 3 or 32..512 input and 32..512 output channels in steps of 32, got %d -> %d", Cin, Cout);
+    MVS_REQUIRE(w && ws, MVS_ERR_NULL, "conv2d_wide_pack_weights: null pointer argument");
+    const int total = (int)c2w_packed_floats(Cin, Cout);
+    MVS_LAUNCH(conv2d_wide_pack_kernel, dim3(mvs_cdiv(total, 256)), dim3(256), 0, stream, w, ws, Cin, Cout, c2w_nbp(Cout), total, w_channels_last ? 1 : 0);
+    return mvs_check_launch("conv2d_wide pack");
+}
+
+static int c2w_pool(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream) {
+    const long long quads = (long long)N * (H / 2) * (W / 2) * (C / 4);
+    MVS_LAUNCH(maxpool2x2_cl_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, x, y, H, W, C, quads);
+    return mvs_check_launch("pool2x2");
+}
+
+// x [N,H,W,C] -> y [N,H/2,W/2,C] (floor), C a multiple of 4
+extern "C" int mvs_maxpool2x2_cl(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream) {
+    MVS_REQUIRE(N > 0 && H >= 2 && W >= 2 && C > 0 && (long long)N * H * W * C < (1LL << 40), MVS_ERR_SHAPE,
+                "maxpool2x2_cl: bad shape N=%d H=%d W=%d C=%d", N, H, W, C);
+    MVS_REQUIRE(C % 4 == 0, MVS_ERR_UNSUPPORTED, "maxpool2x2_cl: the channel count must be a multiple of 4, got %d", C);
+    MVS_REQUIRE(x && y, MVS_ERR_NULL, "maxpool2x2_cl: null pointer argument");
+    return c2w_pool(x, y, N, H, W, C, stream);
+}
+
+// x [N,C,H,W] (contiguous) -> y [N,oh,ow,C]
+extern "C" int mvs_resize_bilinear_cl(const float* x, float* y, int N, int C, int H, int W, int oh, int ow, hipStream_t stream) {
+    MVS_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && oh > 0 && ow > 0 && (long long)N * C * H * W < (1LL << 40) &&
+                (long long)N * C * oh * ow < (1LL << 40), MVS_ERR_SHAPE, "resize_bilinear_cl: bad shape N=%d C=%d %dx%d -> %dx%d", N, C, H, W, oh, ow);
+    MVS_REQUIRE(x && y, MVS_ERR_NULL, "resize_bilinear_cl: null pointer argument");
+    const long long total = (long long)N * oh * ow * C;
+    MVS_LAUNCH(resize_bilinear_cl_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, x, y, C, H, W, oh, ow,
+               (float)H / (float)oh, (float)W / (float)ow, total);
+    return mvs_check_launch("resize_cl");
+}
+
+static const char* const C2W_SPLIT_LABEL[9] = {"", "", "conv2d_wide splitk=2", "conv2d_wide splitk=3", "conv2d_wide splitk=4", "conv2d_wide splitk=5",
+                                               "conv2d_wide splitk=6", "conv2d_wide splitk=7", "conv2d_wide splitk=8"};
+
+// one layer, arguments already checked: convolution (-> y, or -> ws in front of a pool; partial images behind it in ws), the
+// fixed-order sum of a split-K launch, the pool
+static int c2w_run(const float* x, const float* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin, int Cout,
+                   int relu, int pool, hipStream_t stream) {
+    const long long M = (long long)N * H * W;
+    const C2wPlan p = c2w_plan(M, Cin, Cout);
+    MVS_REQUIRE(ws || (!pool && p.split == 1), MVS_ERR_NULL, "conv2d_wide_fwd: this call needs its workspace (pool or split-K), got a null pointer");
+    float* full = pool ? ws : y;
+    float* part = ws + (pool ? M * Cout : 0);
+    Conv2dWideArgs a = {};
+    a.x = x; a.wp = packed; a.bias = bias; a.y = p.split > 1 ? part : full;
+    a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.M = (int)M;
+    a.nbp = c2w_nbp(Cout); a.nsteps = c2w_nsteps(Cin); a.split = p.split; a.relu = relu ? 1 : 0;
+    const dim3 grid((unsigned)((M + 32 * p.mb - 1) / (32 * p.mb)), a.nbp / 4, p.split);
+    int rc;
+    if (Cin == 3) {
+        MVS_LAUNCH((conv2d_wide_kernel<4, true>), grid, dim3(256), 0, stream, a);
+        rc = mvs_check_launch("conv2d_wide cin3");
+    } else if (p.mb == 4) {
+        MVS_LAUNCH((conv2d_wide_kernel<4, false>), grid, dim3(256), 0, stream, a);
+        rc = mvs_check_launch(p.split > 1 ? C2W_SPLIT_LABEL[p.split] : "conv2d_wide t128x64");
+    } else {
+        MVS_LAUNCH((conv2d_wide_kernel<2, false>), grid, dim3(256), 0, stream, a);
+        rc = mvs_check_launch(p.split > 1 ? C2W_SPLIT_LABEL[p.split] : "conv2d_wide t64x64");
+    }
+    if (rc) return rc;
+    if (p.split > 1) {
+        const long long quads = M * Cout / 4;
+        MVS_LAUNCH(conv2d_wide_reduce_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, stream, part, bias, full, quads, Cout, p.split, a.relu);
+        rc = mvs_check_launch("conv2d_wide reduce");
+        if (rc) return rc;
+    }
+    return pool ? c2w_pool(full, y, N, H, W, Cout, stream) : MVS_OK;
+}
+
+#define MVS_TRUNK_MAX_LAYERS 32
+struct MvsTrunkLayer {                // == include/mvs_hip.h
+    int cin, cout, relu, pool_after;
+};
+
+static bool c2w_aligned(const void* p) { return ((size_t)p & 15) == 0; }
+
+// x [N,H,W,Cin] -> y [N,H,W,Cout], or [N,H/2,W/2,Cout] with pool; packed: mvs_conv2d_wide_pack_weights; bias [Cout] or null
+extern "C" int mvs_conv2d_wide_fwd(const float* x, const float* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin,
+                                   int Cout, int relu, int pool, hipStream_t stream) {
+    int rc = c2w_check("conv2d_wide_fwd", N, H, W, Cin, Cout);
+    if (rc) return rc;
+    MVS_REQUIRE(!pool || (H >= 2 && W >= 2), MVS_ERR_SHAPE, "conv2d_wide_fwd: a %dx%d map cannot be pooled", H, W);
+    MVS_REQUIRE(x && packed && y, MVS_ERR_NULL, "conv2d_wide_fwd: null pointer argument");
+    MVS_REQUIRE(c2w_aligned(x) && c2w_aligned(packed) && c2w_aligned(bias) && c2w_aligned(y) && c2w_aligned(ws), MVS_ERR_UNSUPPORTED,
+                "conv2d_wide_fwd: pointers must be 16-byte aligned");
+    return c2w_run(x, packed, bias, y, ws, N, H, W, Cin, Cout, relu, pool, stream);
+}
+
+// The whole trunk: layer i reads x (i = 0) or the previous layer's output and writes buf_a / buf_b in turn, the last one `out`
+// ([N,h,w,Cout_last], the [N h w, C] matrix the NMF reads).  The same kernels in the same order as n mvs_conv2d_wide_fwd calls.
+// buf_a, buf_b: each at least the largest output of layers 0 .. n-2; ws: the largest mvs_conv2d_wide_workspace_floats of the chain.
+extern "C" int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const float* const* packed, const float* const* bias, const float* x,
+                                  float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, hipStream_t stream) {
+    MVS_REQUIRE(n >= 1 && n <= MVS_TRUNK_MAX_LAYERS, MVS_ERR_SHAPE, "conv_trunk_fwd: 1..%d layers, got %d", MVS_TRUNK_MAX_LAYERS, n);
+    MVS_REQUIRE(layers && packed && bias && x && out && ws && (n == 1 || (buf_a && buf_b)), MVS_ERR_NULL, "conv_trunk_fwd: null pointer argument");
+    MVS_REQUIRE(c2w_aligned(x) && c2w_aligned(buf_a) && c2w_aligned(buf_b) && c2w_aligned(ws) && c2w_aligned(out), MVS_ERR_UNSUPPORTED,
+                "conv_trunk_fwd: pointers must be 16-byte aligned");
+    int h = H, w = W;
+    for (int i = 0; i < n; ++i) {          // everything is checked before the first launch
+        const MvsTrunkLayer& l = layers[i];
+        int rc = c2w_check("conv_trunk_fwd", N, h, w, l.cin, l.cout);
+        if (rc) return rc;
+        MVS_REQUIRE(i == 0 || l.cin == layers[i - 1].cout, MVS_ERR_SHAPE, "conv_trunk_fwd: layer %d takes %d channels, layer %d makes %d", i, l.cin,
+                    i - 1, layers[i - 1].cout);
+        MVS_REQUIRE(packed[i] && c2w_aligned(packed[i]) && c2w_aligned(bias[i]), MVS_ERR_NULL, "conv_trunk_fwd: layer %d: null or unaligned weight image / bias", i);
+        if (l.pool_after) {
+            MVS_REQUIRE(h >= 2 && w >= 2, MVS_ERR_SHAPE, "conv_trunk_fwd: layer %d: a %dx%d map cannot be pooled", i, h, w);
+            h /= 2; w /= 2;
+        }
+    }
+    h = H; w = W;
+    const float* src = x;
+    for (int i = 0; i < n; ++i) {
+        const MvsTrunkLayer& l = layers[i];
+        float* dst = i == n - 1 ? out : ((i & 1) ? buf_b : buf_a);
+        int rc = c2w_run(src, packed[i], bias[i], dst, ws, N, h, w, l.cin, l.cout, l.relu, l.pool_after, stream);
+        if (rc) return rc;
+        if (l.pool_after) { h /= 2; w /= 2; }
+        src = dst;
+    }
+    return MVS_OK;
 }

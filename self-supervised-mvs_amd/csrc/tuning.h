@@ -53,7 +53,12 @@
     X(conv2d_pp,        1,    0, 1,       "3x3 stride-1 layers with <= 8 output channels as pixel-pair GEMMs (conv2d_igemm_kernel<.., PP>)") \
     X(conv2d_s2_mfma,   2,    0, 2,       "stride-2 input gradient: 2 ONE four-class MFMA pass with compacted taps, 1 four parity-class passes, 0 direct VALU form") \
     X(wgrad2d_groups,   256,  0, 1 << 20, "persistent workgroups of the weight gradient (used: 1 .. 1024; 256 = one per CU)") \
-    X(wgrad2d_batch,    2048, 1, 4096,    "workgroups of the batched weight gradient (both launches together), shared out by work")
+    X(wgrad2d_batch,    2048, 1, 4096,    "workgroups of the batched weight gradient (both launches together), shared out by work") \
+    /* wide forward 2-D convolutions of the frozen trunk (conv2d_wide_kernels.h) */ \
+    X(c2w_tile,         0,    0, 2,       "0 = t128x64 when its launch has at least c2w_big_min workgroups, else t64x64; 1 = always t64x64; 2 = always t128x64") \
+    X(c2w_big_min,      512,  0, 1 << 30, "... workgroups (two per CU)") \
+    X(c2w_splitk,       0,    0, 8,       "K ranges of a layer: 0 = doubled (<= 8) while a t64x64 launch has fewer than c2w_split_min workgroups, 1 = never split, 2..8 = this many") \
+    X(c2w_split_min,    512,  0, 1 << 30, "... workgroups (two per CU)")
 
 struct MvsTuning {
 #define MVS_KNOB_FIELD(key, def, lo, hi, doc) int key;

@@ -3,8 +3,12 @@
 Same call signatures and return values as the reference (seg_dff.py:50-143).  The multiplicative-update solver -- a dozen small
 launches per iteration and a host synchronisation at every tenth one in the reference -- is one ``ops.nmf_solve`` call for the
 whole batch (csrc/seg_loss_kernels.h: two launches per iteration, the stopping decision taken on the device) and its status is
-read back once per batch.  The feature extractor stays a stock PyTorch call: a frozen, pretrained third-party network under
-``no_grad``, not part of this path.
+read back once per batch.  The feature extractor -- a frozen network under ``no_grad`` -- has two routes: the stock PyTorch
+call (``F.interpolate`` + ``net.features`` + a layout change), and, for a trunk of 3x3 convolutions, ReLUs and 2x2 max pools
+(``trunk_served``: VGG19's shape), the HIP route ``ops.resize_bilinear_cl`` + ``ops.conv_trunk_forward``
+(csrc/conv2d_wide_kernels.h), whose last output already is the matrix the NMF reads.  ``SegDFF(hip_features=...)`` chooses;
+DESIGN.md section 7 has the measurement behind the default.  ``vgg19_trunk(state_dict)`` builds VGG19's feature trunk with
+torchvision's parameter names without torchvision.
 
 Differences from the reference, on purpose: the initial factors come from a private ``torch.Generator``
 (the reference re-seeds the global generator and then restores the *initial* seed, a side effect not copied); a solve whose W
@@ -48,12 +52,108 @@ def NMF(V, k, W=None, H=None, random_seed=None, max_iter=200, tol=1e-4, cuda=Tru
     return Wr, Hr
 
 
+# VGG19's feature trunk (Simonyan & Zisserman 2015, configuration E): output channels of the 3x3 convolutions, "M" = 2x2 max pool.
+# The last pool of the published table is left out, as SegDFF does not use it.
+VGG19_LAYERS = (64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512)
+
+
+class _Trunk(nn.Module):
+    def __init__(self, features):
+        super().__init__()
+        self.features = features
+
+    def forward(self, x):
+        return self.features(x)
+
+
+def conv_trunk(layers, in_channels=3):
+    """``.features`` = nn.Sequential of Conv2d(3x3, pad 1) + ReLU per number and MaxPool2d(2, 2) per "M" of ``layers``, initialised as
+    torchvision initialises VGG (kaiming_normal_(fan_out, relu), bias 0), parameters frozen."""
+    mods, cin = [], in_channels
+    for v in layers:
+        if v == "M":
+            mods.append(nn.MaxPool2d(kernel_size=2, stride=2))
+        else:
+            conv = nn.Conv2d(cin, v, kernel_size=3, padding=1)
+            nn.init.kaiming_normal_(conv.weight, mode="fan_out", nonlinearity="relu")
+            nn.init.constant_(conv.bias, 0)
+            mods += [conv, nn.ReLU(inplace=True)]
+            cin = v
+    net = _Trunk(nn.Sequential(*mods))
+    for p in net.parameters():
+        p.requires_grad_(False)
+    return net
+
+
+def vgg19_trunk(state_dict=None):
+    """VGG19's feature extractor without its last pool, built here (no torchvision): ``.features`` has torchvision's indices --
+    convolutions at 0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28, 30, 32, 34, each followed by a ReLU, MaxPool2d(2, 2) at 4, 9,
+    18, 27, no entry 36 -- so a VGG19 weight file a user already has loads without renaming: ``state_dict`` may be the whole
+    model's (``features.*`` are taken, the classifier's and ``features.36``-less extras ignored) or just the trunk's.  Without
+    one the weights are random (torchvision's initialisation); nothing is downloaded."""
+    net = conv_trunk(VGG19_LAYERS)
+    if state_dict is not None:
+        own = net.state_dict()
+        picked = {k: v for k, v in state_dict.items() if k in own}
+        missing = sorted(set(own) - set(picked))
+        if missing:
+            raise KeyError("vgg19_trunk: the state dict lacks %s" % ", ".join(missing))
+        net.load_state_dict(picked)
+    return net.eval()
+
+
+def trunk_layers(net):
+    """[(Conv2d, relu, pool_after)] when ``net.features`` is an nn.Sequential the HIP trunk serves, else None: only Conv2d (3x3,
+    stride 1, padding 1, dilation 1, groups 1, zeros padding, 3 or 32..512 input and 32..512 output channels in steps of 32),
+    each optionally followed directly by a ReLU, and MaxPool2d(2, 2, ceil_mode=False) directly after a ReLU."""
+    feats = getattr(net, "features", None)
+    if not isinstance(feats, nn.Sequential) or len(feats) == 0:
+        return None
+    mods, layers, i = list(feats), [], 0
+    while i < len(mods):
+        m = mods[i]
+        if type(m) is not nn.Conv2d:
+            return None
+        if (tuple(m.kernel_size), tuple(m.stride), tuple(m.dilation), m.groups, m.padding_mode) != ((3, 3), (1, 1), (1, 1), 1, "zeros") \
+                or m.padding not in ((1, 1), 1, "same") or not ops.conv2d_wide_serves(m.in_channels, m.out_channels) \
+                or m.weight.dtype != torch.float32:
+            return None
+        i += 1
+        relu = i < len(mods) and type(mods[i]) is nn.ReLU
+        i += relu
+        pool = False
+        if relu and i < len(mods) and type(mods[i]) is nn.MaxPool2d:
+            p = mods[i]
+            two = lambda v: v in (2, (2, 2))
+            if not (two(p.kernel_size) and two(p.stride) and p.padding in (0, (0, 0)) and p.dilation in (1, (1, 1)) and not p.ceil_mode
+                    and not p.return_indices):
+                return None
+            pool = True
+            i += 1
+        layers.append((m, relu, pool))
+    if any(a[0].out_channels != b[0].in_channels for a, b in zip(layers, layers[1:])):
+        return None
+    return layers
+
+
+def trunk_served(net):
+    """True when ``net.features`` can run on the HIP trunk (``trunk_layers``)."""
+    return trunk_layers(net) is not None
+
+
 class SegDFF(nn.Module):
     """imgs [B,N,3,H,W] -> heatmaps [B,N,h,w,K] (requires_grad False): deep feature factorisation of the frozen network's
     features, one NMF problem per batch item (seg_dff.py:109-143).  net: the feature extractor (its ``.features`` is applied
-    to the 224x224 images); None = torchvision's pretrained VGG19 without ``features['36']``, as in the reference."""
+    to the 224x224 images); None = torchvision's pretrained VGG19 without ``features['36']``, as in the reference.
+    hip_features: False = the stock PyTorch call; True = the HIP trunk (raises when ``trunk_served(net)`` is false); None = the
+    HIP trunk when it is served, the images are on the GPU and HIP_FEATURES_DEFAULT says so."""
 
-    def __init__(self, K, max_iter=50, net=None):
+    # what ``hip_features=None`` does with a served trunk on the GPU: set by the measurement of tools/vgg_features_bench.py
+    # (profiles/vgg_features_timing.json) under the rule "HIP only when its p90 is below the stock path's p10": N = 7 on one
+    # MI355X, HIP 3.088 ms (p90 3.104) against 3.182 ms (p10 3.168) for the stock path
+    HIP_FEATURES_DEFAULT = True
+
+    def __init__(self, K, max_iter=50, net=None, hip_features=None):
         super().__init__()
         self.K = K
         self.max_iter = max_iter
@@ -61,11 +161,44 @@ class SegDFF(nn.Module):
             try:
                 from torchvision import models
             except ImportError as exc:
-                raise ImportError("SegDFF needs torchvision for its pretrained VGG19 feature extractor (or pass net=...): "
-                                  "torchvision cannot be imported (%s)" % exc) from exc
+                raise ImportError("SegDFF needs torchvision for its pretrained VGG19 feature extractor: torchvision cannot be "
+                                  "imported (%s).  Without torchvision pass net=vgg19_trunk(state_dict=...) with a VGG19 weight "
+                                  "file of your own (torchvision's key names), or any other net=..." % exc) from exc
             net = models.vgg19(pretrained=True)
             del net.features._modules['36']  # the last pooling layer is not used
         self.net = net
+        if hip_features and not trunk_served(net):
+            raise ValueError("SegDFF(hip_features=True): net.features is not a trunk the HIP kernels serve (3x3 stride-1 pad-1 "
+                             "convolutions with 3 or 32..512 -> 32..512 channels in steps of 32, ReLU, MaxPool2d(2, 2))")
+        self.hip_features = hip_features
+
+    def _hip_route(self, imgs):
+        if self.hip_features is False:
+            return None
+        if self.hip_features is None and not (self.HIP_FEATURES_DEFAULT and imgs.is_cuda):
+            return None
+        layers = trunk_layers(self.net)
+        if layers is None:
+            if self.hip_features:
+                raise ValueError("SegDFF(hip_features=True): net.features is no longer a trunk the HIP kernels serve")
+            return None
+        return layers
+
+    def _features(self, imgs):
+        """imgs [B,N,3,H,W] -> (flat [B, N h w, C], h, w)"""
+        b, nv = imgs.shape[:2]
+        x = imgs.reshape(b * nv, *imgs.shape[2:])
+        layers = self._hip_route(imgs)
+        if layers is not None:
+            x = ops.resize_bilinear_cl(x.float(), (224, 224))
+            plan = ops.trunk_plan([(m.weight, m.bias, relu, pool) for m, relu, pool in layers], x.shape, x)
+            feats = ops.conv_trunk_forward(plan, x)                    # [N,h,w,C]: the NMF's layout already
+            h, w, c = feats.shape[1:]
+            return feats.view(b, nv * h * w, c), h, w
+        x = F.interpolate(x, size=(224, 224), mode='bilinear', align_corners=False)
+        features = self.net.features(x)
+        c, h, w = features.shape[1:]
+        return features.permute(0, 2, 3, 1).reshape(b, nv * h * w, c).float().contiguous(), h, w
 
     def _solve(self, flat, seeds):
         """flat [P,n,m], one seed per problem -> W [P,n,K], status [P,4]: one kernel call for all problems"""
@@ -78,10 +211,7 @@ class SegDFF(nn.Module):
     def forward(self, imgs):
         b, nv = imgs.shape[:2]
         with torch.no_grad():
-            x = F.interpolate(imgs.reshape(b * nv, *imgs.shape[2:]), size=(224, 224), mode='bilinear', align_corners=False)
-            features = self.net.features(x)
-            c, h, w = features.shape[1:]
-            flat = features.permute(0, 2, 3, 1).reshape(b, nv * h * w, c).float().contiguous()
+            flat, h, w = self._features(imgs)
             W, status = self._solve(flat, [1] * b)
             bad = (status[:, 1] > 0).nonzero().flatten().tolist()     # the one status read of the batch
             attempt = 1

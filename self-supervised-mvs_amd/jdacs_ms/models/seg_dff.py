@@ -1,2 +1,3 @@
 """Drop-in for jdacs-ms/models/seg_dff.py: the same NMF / SegDFF as jdacs (mvs_amd.jdacs.models.seg_dff), re-exported."""
-from ...jdacs.models.seg_dff import MAX_ATTEMPTS, NMF, SegDFF, initial_factors  # noqa: F401
+from ...jdacs.models.seg_dff import (MAX_ATTEMPTS, NMF, VGG19_LAYERS, SegDFF, conv_trunk, initial_factors, trunk_layers,  # noqa: F401
+                                     trunk_served, vgg19_trunk)

@@ -2300,3 +2300,163 @@ class Conv2dLReLUFn(torch.autograd.Function):
         gw = conv2d_wgrad(x, g, tuple(weight.shape), 1) if ctx.needs_input_grad[1] else None
         gb = g.sum(dim=(0, 2, 3)) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return gx, gw, gb, None
+
+
+# ------------------------------------------------------------------------------------------------
+# Wide forward 2-D convolutions: the frozen VGG-style trunk in front of the NMF (csrc/conv2d_wide_kernels.h).  Forward only;
+# tensors of this family are PHYSICALLY [N,H,W,C] (contiguous), the layout the NMF reads.
+# ------------------------------------------------------------------------------------------------
+def _frozen(what, *tensors):
+    """the trunk is frozen: there is no backward pass to record"""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
+        raise RuntimeError("%s is forward only (a frozen trunk): an input requires grad -- call it under torch.no_grad() or "
+                           "detach the inputs" % what)
+
+
+def conv2d_wide_serves(cin: int, cout: int) -> bool:
+    """3 or 32..512 input channels and 32..512 output channels, in steps of 32"""
+    return (cin == 3 or (32 <= cin <= 512 and cin % 32 == 0)) and 32 <= cout <= 512 and cout % 32 == 0
+
+
+def _wide_pack(lib, weight, like):
+    cout, cin, kh, kw = weight.shape
+    nfl = lib.raw("mvs_conv2d_wide_packed_floats", cin, cout) if (kh, kw) == (3, 3) else -1
+    if nfl < 0:
+        raise ValueError("conv2d_wide: serves 3x3 layers with 3 or 32..512 input and 32..512 output channels in steps of 32, got "
+                         "weight %s" % (tuple(weight.shape),))
+    w = weight.detach()
+    wl = _w_layout(w)
+    if wl is None:
+        w, wl = w.contiguous(), 0        # (kept in a local: the pointer must stay valid until the call has been made)
+    packed = torch.empty(nfl, dtype=torch.float32, device=like.device)
+    lib.call("mvs_conv2d_wide_pack_weights", _p(w), _p(packed), cin, cout, wl, _stream(like), tag=("pack2d_wide:%d>%d", cin, cout))
+    return packed
+
+
+def _wide_ws_floats(lib, n, h, w, cin, cout):
+    nfl = lib.raw("mvs_conv2d_wide_workspace_floats", n, h, w, cin, cout)
+    if nfl < 0:
+        raise ValueError("conv2d_wide: unsupported shape N=%d H=%d W=%d Cin=%d Cout=%d" % (n, h, w, cin, cout))
+    return int(nfl)
+
+
+def conv2d_wide_forward(x_cl, weight, bias=None, relu=False, pool=False):
+    """x_cl [N,H,W,Cin] (contiguous), weight [Cout,Cin,3,3] (contiguous or channels-last in memory, read in place), bias [Cout] or
+    None -> [relu](conv3x3(x, pad 1) + bias) as [N,H,W,Cout], or [N,H//2,W//2,Cout] with pool (2x2 max pool, stride 2, floor).
+    Forward only.  The weight image is packed by every call: a trunk packs once (conv_trunk_forward)."""
+    lib = _lib_for(x_cl)
+    _frozen("conv2d_wide_forward", x_cl, weight, bias)
+    if x_cl.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x_cl.shape[3]:
+        raise ValueError("conv2d_wide_forward: x [N,H,W,Cin] and weight [Cout,Cin,3,3] expected, got %s / %s"
+                         % (tuple(x_cl.shape), tuple(weight.shape)))
+    _lib_for(weight)
+    x = x_cl.detach().contiguous()
+    n, h, w, cin = x.shape
+    cout = weight.shape[0]
+    packed = _wide_pack(lib, weight, x)
+    ws = torch.empty(_wide_ws_floats(lib, n, h, w, cin, cout), dtype=torch.float32, device=x.device)
+    if pool and (h < 2 or w < 2):
+        raise ValueError("conv2d_wide_forward: a %dx%d map cannot be pooled" % (h, w))
+    y = torch.empty((n, h // 2, w // 2, cout) if pool else (n, h, w, cout), dtype=torch.float32, device=x.device)
+    bias_c = None if bias is None else bias.detach().contiguous()
+    lib.call("mvs_conv2d_wide_fwd", _p(x), _p(packed), _p(bias_c), _p(y), _p(ws), n, h, w, cin, cout, int(bool(relu)), int(bool(pool)),
+             _stream(x), tag=("fwd2d_wide:%d>%d:%dx%dx%d", cin, cout, n, h, w))
+    return y
+
+
+def maxpool2x2_cl(x_cl):
+    """x_cl [N,H,W,C] (contiguous, C a multiple of 4) -> [N,H//2,W//2,C]: 2x2 max pool, stride 2.  Forward only."""
+    lib = _lib_for(x_cl)
+    _frozen("maxpool2x2_cl", x_cl)
+    x = x_cl.detach().contiguous()
+    n, h, w, c = x.shape
+    y = torch.empty((n, h // 2, w // 2, c), dtype=torch.float32, device=x.device)
+    lib.call("mvs_maxpool2x2_cl", _p(x), _p(y), n, h, w, c, _stream(x), tag=("pool2x2:%d:%dx%dx%d", c, n, h, w))
+    return y
+
+
+def resize_bilinear_cl(x, size):
+    """x [N,C,H,W] -> [N,oh,ow,C] (contiguous), the values of F.interpolate(x, size, mode='bilinear', align_corners=False): the resize
+    and the change to the trunk's layout in one pass.  Forward only."""
+    lib = _lib_for(x)
+    _frozen("resize_bilinear_cl", x)
+    if x.dim() != 4:
+        raise ValueError("resize_bilinear_cl: x [N,C,H,W] expected, got %s" % (tuple(x.shape),))
+    oh, ow = (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
+    x = x.detach().contiguous()
+    n, c, h, w = x.shape
+    y = torch.empty((n, oh, ow, c), dtype=torch.float32, device=x.device)
+    lib.call("mvs_resize_bilinear_cl", _p(x), _p(y), n, c, h, w, oh, ow, _stream(x), tag=("resize_cl:%dx%d>%dx%d", h, w, oh, ow))
+    return y
+
+
+_TRUNK_PLANS = {}
+_TRUNK_KNOBS = ("c2w_tile", "c2w_big_min", "c2w_splitk", "c2w_split_min")
+
+
+class _TrunkPlan:
+    """Everything of a frozen trunk that is the same every step for one input shape [N,H,W,Cin]: the C layer table, the packed weight
+    images (made once, here), the two ping-pong activation buffers and the workspace.  The buffers belong to the plan: two
+    forwards of the same plan are ordered by the stream they are enqueued on."""
+
+    def __init__(self, lib, layers, xshape, like):
+        n, h, w, cin = xshape
+        self.n_layers = len(layers)
+        self.xshape = tuple(xshape)
+        self.table = (_lib.MvsTrunkLayer * len(layers))()
+        self.packed, self.bias = [], []
+        ws_floats, buf_floats = 1, 1
+        for i, (weight, bias, relu, pool) in enumerate(layers):
+            cout, cin_w = weight.shape[:2]
+            if cin_w != cin:
+                raise ValueError("conv_trunk: layer %d takes %d channels, its input has %d" % (i, cin_w, cin))
+            t = self.table[i]
+            t.cin, t.cout, t.relu, t.pool_after = cin, cout, int(bool(relu)), int(bool(pool))
+            self.packed.append(_wide_pack(lib, weight, like))
+            self.bias.append(None if bias is None else bias.detach().contiguous().clone())
+            ws_floats = max(ws_floats, _wide_ws_floats(lib, n, h, w, cin, cout))
+            if pool:
+                if h < 2 or w < 2:
+                    raise ValueError("conv_trunk: layer %d: a %dx%d map cannot be pooled" % (i, h, w))
+                h, w = h // 2, w // 2
+            if i < len(layers) - 1:
+                buf_floats = max(buf_floats, n * h * w * cout)
+            cin = cout
+        self.out_shape = (n, h, w, cin)
+        self.packed_ptrs = _ptr_array(self.packed)
+        self.bias_ptrs = (C.c_void_p * len(layers))(*[_p(b) for b in self.bias])
+        self.buf_a = torch.empty(buf_floats, dtype=torch.float32, device=like.device)
+        self.buf_b = torch.empty(buf_floats, dtype=torch.float32, device=like.device)
+        self.ws = torch.empty(ws_floats, dtype=torch.float32, device=like.device)
+
+
+def trunk_plan(layers, xshape, like):
+    """layers: [(weight [Cout,Cin,3,3], bias [Cout] or None, relu, pool_after)] of a frozen trunk; xshape (N,H,W,Cin).  The plan is
+    cached on the input shape, the device and every parameter's data_ptr() and _version: a load_state_dict or any other in-place
+    edit of a parameter makes a new plan (and packs again); an unchanged trunk packs once."""
+    lib = _lib_for(like)
+    _frozen("conv_trunk_forward", *[t for l in layers for t in l[:2]])
+    key = (tuple(int(v) for v in xshape), str(like.device), tuple(lib.get_tuning(k) for k in _TRUNK_KNOBS),
+           tuple((wt.data_ptr(), wt._version, tuple(wt.shape), _w_layout(wt), None if b is None else (b.data_ptr(), b._version), bool(r), bool(p))
+                 for wt, b, r, p in layers))
+    plan = _TRUNK_PLANS.get(key)
+    if plan is None:
+        if len(_TRUNK_PLANS) >= 4:       # (a plan holds its activation buffers: a stale one is 100s of MB)
+            _TRUNK_PLANS.clear()
+        plan = _TRUNK_PLANS[key] = _TrunkPlan(lib, layers, key[0], like)
+    return plan
+
+
+def conv_trunk_forward(plan, x):
+    """x [N,H,W,Cin] (contiguous, e.g. resize_bilinear_cl's output) -> the trunk's last output [N,h,w,C] (a fresh tensor) by ONE C
+    call (mvs_conv_trunk_fwd).  Forward only."""
+    lib = _lib_for(x)
+    _frozen("conv_trunk_forward", x)
+    if tuple(x.shape) != plan.xshape:
+        raise ValueError("conv_trunk_forward: the plan was made for input %s, got %s" % (plan.xshape, tuple(x.shape)))
+    x = x.detach().contiguous()
+    out = torch.empty(plan.out_shape, dtype=torch.float32, device=x.device)
+    n, h, w, _ = plan.xshape
+    lib.call("mvs_conv_trunk_fwd", plan.n_layers, plan.table, plan.packed_ptrs, plan.bias_ptrs, _p(x), _p(plan.buf_a), _p(plan.buf_b),
+             _p(plan.ws), _p(out), n, h, w, _stream(x), tag=("trunk_fwd:%d:%dx%dx%d", plan.n_layers, n, h, w))
+    return out
