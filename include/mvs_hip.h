@@ -443,7 +443,20 @@ int mvs_feature_bwd(int n, const MvsFeatBlock* blocks, int N, int G, const float
  * mvs_conv_trunk_fwd: n layers as ONE call -- layer i reads x (i = 0) or the previous output and writes buf_a / buf_b in turn, the last
  *   layer writes out [N,h,w,Cout_last]; packed[i] / bias[i] (NULL entries allowed in bias) per layer; buf_a, buf_b: each the largest
  *   output of layers 0 .. n-2; ws: the largest mvs_conv2d_wide_workspace_floats of the chain.  The same kernels in the same order
- *   as n mvs_conv2d_wide_fwd calls; every layer is checked before the first launch. */
+ *   as n mvs_conv2d_wide_fwd calls; every layer is checked before the first launch.
+ *
+ * The *_arith entries (csrc/conv2d_wide_bf16_kernels.h) take the ARITHMETIC of the multiplications as an argument -- an argument and
+ * not a tuning knob, because the packed weight image depends on it.  fp32 in, fp32 out and fp32 accumulation in every mode:
+ *   MVS_ARITH_F32     the entries without the suffix (same kernels, same bits, same trace labels);
+ *   MVS_ARITH_BF16    the bf16 MFMA on operands rounded to nearest-even bf16, one product per multiplication.
+ * Any other value is MVS_ERR_UNSUPPORTED (1 was the three-term split "bf16x3": measured, not faster than fp32, not shipped --
+ * DESIGN.md section 7).  A layer with Cin = 3 runs the fp32 "conv2d_wide cin3" arm (and takes the fp32 image) in every mode.
+ * Trace labels of the other layers: "conv2d_wide bf16 pack" / "conv2d_wide bf16 t128x64" / "... t64x64" / "... splitk=N"
+ * (+ "conv2d_wide reduce").  The weight image, the workspace and the forward call of one layer
+ * must be given the same arith: mvs_conv2d_wide_packed_bytes_arith (BYTES; -1 outside the served set or for an unknown arith),
+ * mvs_conv2d_wide_workspace_floats_arith, mvs_conv2d_wide_pack_weights_arith, mvs_conv2d_wide_fwd_arith, mvs_conv_trunk_fwd_arith. */
+#define MVS_ARITH_F32 0
+#define MVS_ARITH_BF16 2
 #define MVS_TRUNK_MAX_LAYERS 32
 typedef struct MvsTrunkLayer {
     int cin, cout, relu, pool_after;
@@ -457,6 +470,13 @@ int mvs_maxpool2x2_cl(const float* x, float* y, int N, int H, int W, int C, hipS
 int mvs_resize_bilinear_cl(const float* x, float* y, int N, int C, int H, int W, int oh, int ow, hipStream_t stream);
 int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const float* const* packed, const float* const* bias, const float* x,
                        float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, hipStream_t stream);
+long long mvs_conv2d_wide_packed_bytes_arith(int Cin, int Cout, int arith);
+long long mvs_conv2d_wide_workspace_floats_arith(int N, int H, int W, int Cin, int Cout, int arith);
+int mvs_conv2d_wide_pack_weights_arith(const float* w, void* ws, int Cin, int Cout, int w_channels_last, int arith, hipStream_t stream);
+int mvs_conv2d_wide_fwd_arith(const float* x, const void* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin,
+                              int Cout, int relu, int pool, int arith, hipStream_t stream);
+int mvs_conv_trunk_fwd_arith(int n, const MvsTrunkLayer* layers, const void* const* packed, const float* const* bias, const float* x,
+                             float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, int arith, hipStream_t stream);
 
 /* ---- geometric-consistency filter on the path's depth maps ---------------------------------------------
  * Replaces reproject_with_depth + check_geometric_consistency (jdacs/eval.py:169-224) for ALL source views of one

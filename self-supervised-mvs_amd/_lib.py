@@ -123,6 +123,11 @@ SIGNATURES = {
     "mvs_maxpool2x2_cl": (_i, [_f, _f, _i, _i, _i, _i, _s]),
     "mvs_resize_bilinear_cl": (_i, [_f, _f, _i, _i, _i, _i, _i, _i, _s]),
     "mvs_conv_trunk_fwd": (_i, [_i, C.POINTER(MvsTrunkLayer), _pp, _pp, _f, _f, _f, _f, _f, _i, _i, _i, _s]),
+    "mvs_conv2d_wide_packed_bytes_arith": (_ll, [_i, _i, _i]),
+    "mvs_conv2d_wide_workspace_floats_arith": (_ll, [_i] * 6),
+    "mvs_conv2d_wide_pack_weights_arith": (_i, [_f, _f, _i, _i, _i, _i, _s]),
+    "mvs_conv2d_wide_fwd_arith": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
+    "mvs_conv_trunk_fwd_arith": (_i, [_i, C.POINTER(MvsTrunkLayer), _pp, _pp, _f, _f, _f, _f, _f, _i, _i, _i, _i, _s]),
 }
 
 OP_CONV_FWD, OP_CONV_DGRAD, OP_CONV_WGRAD, OP_CONVT_FWD, OP_CONVT_DGRAD, OP_CONVT_WGRAD = range(6)

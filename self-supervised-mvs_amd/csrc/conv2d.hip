@@ -885,6 +885,7 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_batch_reduce_kernel(Wg2Batch
 }
 
 #include "conv2d_wide_kernels.h"   // the wide forward family of the frozen VGG-style trunk (host side: end of this file)
+#include "conv2d_wide_bf16_kernels.h"   // ... its opt-in arms on the bf16 MFMA (arith = bf16)
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -1351,18 +1352,34 @@ static long long c2w_packed_floats(int Cin, int Cout) { return (long long)c2w_ns
 // 0.371 against 0.300 for 512 -> 512); under that t64x64; and where even t64x64 leaves CUs without a workgroup (512 -> 512 at
 // 14x14: 176 workgroups of 144 k-steps) K is split until the launch has c2w_split_min workgroups, as long as every range keeps
 // at least nine steps (one chunk of 32 input channels): 0.133 ms unsplit, 0.120 / 0.091 / 0.098 with 2 / 4 / 8 ranges.
+//
+// arith (the mvs_*_arith entries; conv2d_wide_bf16_kernels.h): MVS_ARITH_F32 is everything above.  Under MVS_ARITH_BF16 a layer
+// with Cin = 3 still runs the fp32 cin3 arm from the fp32 weight image (one k-step, 16 % of the MFMA peak: not MFMA-bound); every
+// other layer runs conv2d_wide_bf_kernel, its tile chosen by the same rule and c2w_big_min, its K ranges by the same rule with a
+// threshold of its own, c2w_bf_split_min = 2048: a bf16 workgroup has an eighth of the MFMA time per step, so a launch needs more
+// workgroups per CU before splitting K stops paying (measured at N = 7, forced arms, DESIGN.md section 7: 512 -> 512 at 28x28,
+// 688 t64x64 workgroups: 0.083 ms with four K ranges against 0.092 unsplit, 0.085 / 0.091 with two / eight; 256 -> 512 at 28x28:
+// flat from one to four ranges, 0.054 / 0.053 / 0.055, worse with eight; 512 -> 512 at 14x14, 176 workgroups: 0.036 with eight
+// ranges against 0.039 with four).  2048 gives four ranges at both 28x28 shapes and eight at 14x14; the layers on t128x64 are
+// never split.  Fitted to N = 7 only: at N = 1 every t64x64 layer is split as far as nine steps per range allow -- unmeasured.
+#define MVS_ARITH_F32 0               // == include/mvs_hip.h; 1 stays unused and refused: it was bf16x3 (three-term split), measured and not shipped
+#define MVS_ARITH_BF16 2
+static bool c2w_arith_ok(int arith) { return arith == MVS_ARITH_F32 || arith == MVS_ARITH_BF16; }
+static bool c2w_on_bf(int Cin, int arith) { return arith != MVS_ARITH_F32 && Cin != 3; }
+
 struct C2wPlan { int mb, split; };
-static C2wPlan c2w_plan(long long M, int Cin, int Cout) {
+static C2wPlan c2w_plan(long long M, int Cin, int Cout, int arith = MVS_ARITH_F32) {
     const int nsteps = c2w_nsteps(Cin);
     const long long ct = c2w_nbp(Cout) / 4, wg128 = (M + 127) / 128 * ct, wg64 = (M + 63) / 64 * ct;
     C2wPlan p = {2, 1};
     if (Cin == 3) { p.mb = 4; return p; }
     if (g_tune.c2w_tile == 2 || (g_tune.c2w_tile == 0 && wg128 >= g_tune.c2w_big_min)) p.mb = 4;
+    const int split_min = c2w_on_bf(Cin, arith) ? g_tune.c2w_bf_split_min : g_tune.c2w_split_min;
     int split = g_tune.c2w_splitk;
     if (split == 0) {
         split = 1;
         if (p.mb == 2)
-            while (wg64 * split < g_tune.c2w_split_min && split < 8 && nsteps / (2 * split) >= 9) split *= 2;
+            while (wg64 * split < split_min && split < 8 && nsteps / (2 * split) >= 9) split *= 2;
     }
     p.split = split < 1 ? 1 : (split > nsteps ? nsteps : split);
     return p;
@@ -1377,13 +1394,23 @@ static int c2w_check(const char* what, int N, int H, int W, int Cin, int Cout) {
 
 // floats of the `ws` argument of mvs_conv2d_wide_fwd: the full-resolution image in front of a pool, plus the partial images of a
 // split-K launch (the knobs are read now: query right before the call); -1 outside the served set
-extern "C" long long mvs_conv2d_wide_workspace_floats(int N, int H, int W, int Cin, int Cout) {
-    if (N <= 0 || H <= 0 || W <= 0 || (long long)N * H * W >= (1LL << 31) - 256 || !c2w_served(Cin, Cout)) return -1;
+extern "C" long long mvs_conv2d_wide_workspace_floats_arith(int N, int H, int W, int Cin, int Cout, int arith) {
+    if (N <= 0 || H <= 0 || W <= 0 || (long long)N * H * W >= (1LL << 31) - 256 || !c2w_served(Cin, Cout) || !c2w_arith_ok(arith)) return -1;
     const long long M = (long long)N * H * W;
-    const C2wPlan p = c2w_plan(M, Cin, Cout);
+    const C2wPlan p = c2w_plan(M, Cin, Cout, arith);
     return M * Cout * (1 + (p.split > 1 ? p.split : 0));
 }
+extern "C" long long mvs_conv2d_wide_workspace_floats(int N, int H, int W, int Cin, int Cout) {
+    return mvs_conv2d_wide_workspace_floats_arith(N, H, W, Cin, Cout, MVS_ARITH_F32);
+}
 extern "C" long long mvs_conv2d_wide_packed_floats(int Cin, int Cout) { return c2w_served(Cin, Cout) ? c2w_packed_floats(Cin, Cout) : -1; }
+// bytes of the weight image of one layer in one arithmetic (the fp32 image for MVS_ARITH_F32 and for Cin = 3; else one 16-byte
+// fragment per (step, column tile, lane)); -1 outside the served set or for an unknown arith
+extern "C" long long mvs_conv2d_wide_packed_bytes_arith(int Cin, int Cout, int arith) {
+    if (!c2w_served(Cin, Cout) || !c2w_arith_ok(arith)) return -1;
+    if (!c2w_on_bf(Cin, arith)) return c2w_packed_floats(Cin, Cout) * 4;
+    return (long long)c2w_nsteps(Cin) * c2w_nbp(Cout) * 64 * 16;
+}
 
 extern "C" int mvs_conv2d_wide_pack_weights(const float* w, float* ws, int Cin, int Cout, int w_channels_last, hipStream_t stream) {
     MVS_REQUIRE(c2w_served(Cin, Cout), MVS_ERR_UNSUPPORTED,
@@ -1392,6 +1419,23 @@ extern "C" int mvs_conv2d_wide_pack_weights(const float* w, float* ws, int Cin, 
     const int total = (int)c2w_packed_floats(Cin, Cout);
     MVS_LAUNCH(conv2d_wide_pack_kernel, dim3(mvs_cdiv(total, 256)), dim3(256), 0, stream, w, ws, Cin, Cout, c2w_nbp(Cout), total, w_channels_last ? 1 : 0);
     return mvs_check_launch("conv2d_wide pack");
+}
+
+#define C2W_REQUIRE_ARITH(what, arith) \
+    MVS_REQUIRE(c2w_arith_ok(arith), MVS_ERR_UNSUPPORTED, "%s: arith must be 0 (f32) or 2 (bf16), got %d", what, arith)
+
+// ws: mvs_conv2d_wide_packed_bytes_arith(Cin, Cout, arith) bytes, 16-byte aligned
+extern "C" int mvs_conv2d_wide_pack_weights_arith(const float* w, void* ws, int Cin, int Cout, int w_channels_last, int arith, hipStream_t stream) {
+    C2W_REQUIRE_ARITH("conv2d_wide_pack_weights", arith);
+    if (!c2w_on_bf(Cin, arith)) return mvs_conv2d_wide_pack_weights(w, (float*)ws, Cin, Cout, w_channels_last, stream);
+    MVS_REQUIRE(c2w_served(Cin, Cout), MVS_ERR_UNSUPPORTED,
+                "conv2d_wide_pack_weights: serves 3 or 32..512 input and 32..512 output channels in steps of 32, got %d -> %d", Cin, Cout);
+    MVS_REQUIRE(w && ws, MVS_ERR_NULL, "conv2d_wide_pack_weights: null pointer argument");
+    MVS_REQUIRE(((size_t)ws & 15) == 0, MVS_ERR_UNSUPPORTED, "conv2d_wide_pack_weights: the image must be 16-byte aligned");
+    const int total = c2w_nsteps(Cin) * c2w_nbp(Cout) * 64;
+    MVS_LAUNCH(conv2d_wide_bf_pack_kernel, dim3(mvs_cdiv(total, 256)), dim3(256), 0, stream, w, (uint4*)ws, Cin, Cout, c2w_nbp(Cout), total,
+               w_channels_last ? 1 : 0);
+    return mvs_check_launch("conv2d_wide bf16 pack");
 }
 
 static int c2w_pool(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream) {
@@ -1422,13 +1466,18 @@ extern "C" int mvs_resize_bilinear_cl(const float* x, float* y, int N, int C, in
 
 static const char* const C2W_SPLIT_LABEL[9] = {"", "", "conv2d_wide splitk=2", "conv2d_wide splitk=3", "conv2d_wide splitk=4", "conv2d_wide splitk=5",
                                                "conv2d_wide splitk=6", "conv2d_wide splitk=7", "conv2d_wide splitk=8"};
+// [0: t64x64, 1: t128x64, 2..8: that many K ranges]
+static const char* const C2W_BF_LABEL[9] = {"conv2d_wide bf16 t64x64", "conv2d_wide bf16 t128x64", "conv2d_wide bf16 splitk=2", "conv2d_wide bf16 splitk=3",
+                                            "conv2d_wide bf16 splitk=4", "conv2d_wide bf16 splitk=5", "conv2d_wide bf16 splitk=6", "conv2d_wide bf16 splitk=7",
+                                            "conv2d_wide bf16 splitk=8"};
 
 // one layer, arguments already checked: convolution (-> y, or -> ws in front of a pool; partial images behind it in ws), the
 // fixed-order sum of a split-K launch, the pool
-static int c2w_run(const float* x, const float* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin, int Cout,
-                   int relu, int pool, hipStream_t stream) {
+static int c2w_run(const float* x, const void* packed_image, const float* bias, float* y, float* ws, int N, int H, int W, int Cin, int Cout,
+                   int relu, int pool, int arith, hipStream_t stream) {
     const long long M = (long long)N * H * W;
-    const C2wPlan p = c2w_plan(M, Cin, Cout);
+    const C2wPlan p = c2w_plan(M, Cin, Cout, arith);
+    const float* packed = (const float*)packed_image;
     MVS_REQUIRE(ws || (!pool && p.split == 1), MVS_ERR_NULL, "conv2d_wide_fwd: this call needs its workspace (pool or split-K), got a null pointer");
     float* full = pool ? ws : y;
     float* part = ws + (pool ? M * Cout : 0);
@@ -1438,7 +1487,15 @@ static int c2w_run(const float* x, const float* packed, const float* bias, float
     a.nbp = c2w_nbp(Cout); a.nsteps = c2w_nsteps(Cin); a.split = p.split; a.relu = relu ? 1 : 0;
     const dim3 grid((unsigned)((M + 32 * p.mb - 1) / (32 * p.mb)), a.nbp / 4, p.split);
     int rc;
-    if (Cin == 3) {
+    if (c2w_on_bf(Cin, arith)) {
+        Conv2dWideBfArgs b = {};
+        b.x = x; b.wp = (const uint4*)packed_image; b.bias = bias; b.y = a.y;
+        b.H = H; b.W = W; b.Cin = Cin; b.Cout = Cout; b.M = a.M;
+        b.nbp = a.nbp; b.nsteps = a.nsteps; b.split = a.split; b.relu = a.relu;
+        if (p.mb == 4) MVS_LAUNCH(conv2d_wide_bf_kernel<4>, grid, dim3(256), 0, stream, b);
+        else MVS_LAUNCH(conv2d_wide_bf_kernel<2>, grid, dim3(256), 0, stream, b);
+        rc = mvs_check_launch(C2W_BF_LABEL[p.split > 1 ? p.split : (p.mb == 4 ? 1 : 0)]);
+    } else if (Cin == 3) {
         MVS_LAUNCH((conv2d_wide_kernel<4, true>), grid, dim3(256), 0, stream, a);
         rc = mvs_check_launch("conv2d_wide cin3");
     } else if (p.mb == 4) {
@@ -1466,22 +1523,30 @@ struct MvsTrunkLayer {                // == include/mvs_hip.h
 static bool c2w_aligned(const void* p) { return ((size_t)p & 15) == 0; }
 
 // x [N,H,W,Cin] -> y [N,H,W,Cout], or [N,H/2,W/2,Cout] with pool; packed: mvs_conv2d_wide_pack_weights; bias [Cout] or null
-extern "C" int mvs_conv2d_wide_fwd(const float* x, const float* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin,
-                                   int Cout, int relu, int pool, hipStream_t stream) {
+// ... _arith: packed is the image mvs_conv2d_wide_pack_weights_arith made for the same arith
+extern "C" int mvs_conv2d_wide_fwd_arith(const float* x, const void* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin,
+                                         int Cout, int relu, int pool, int arith, hipStream_t stream) {
+    C2W_REQUIRE_ARITH("conv2d_wide_fwd", arith);
     int rc = c2w_check("conv2d_wide_fwd", N, H, W, Cin, Cout);
     if (rc) return rc;
     MVS_REQUIRE(!pool || (H >= 2 && W >= 2), MVS_ERR_SHAPE, "conv2d_wide_fwd: a %dx%d map cannot be pooled", H, W);
     MVS_REQUIRE(x && packed && y, MVS_ERR_NULL, "conv2d_wide_fwd: null pointer argument");
     MVS_REQUIRE(c2w_aligned(x) && c2w_aligned(packed) && c2w_aligned(bias) && c2w_aligned(y) && c2w_aligned(ws), MVS_ERR_UNSUPPORTED,
                 "conv2d_wide_fwd: pointers must be 16-byte aligned");
-    return c2w_run(x, packed, bias, y, ws, N, H, W, Cin, Cout, relu, pool, stream);
+    return c2w_run(x, packed, bias, y, ws, N, H, W, Cin, Cout, relu, pool, arith, stream);
+}
+extern "C" int mvs_conv2d_wide_fwd(const float* x, const float* packed, const float* bias, float* y, float* ws, int N, int H, int W, int Cin,
+                                   int Cout, int relu, int pool, hipStream_t stream) {
+    return mvs_conv2d_wide_fwd_arith(x, packed, bias, y, ws, N, H, W, Cin, Cout, relu, pool, MVS_ARITH_F32, stream);
 }
 
 // The whole trunk: layer i reads x (i = 0) or the previous layer's output and writes buf_a / buf_b in turn, the last one `out`
 // ([N,h,w,Cout_last], the [N h w, C] matrix the NMF reads).  The same kernels in the same order as n mvs_conv2d_wide_fwd calls.
-// buf_a, buf_b: each at least the largest output of layers 0 .. n-2; ws: the largest mvs_conv2d_wide_workspace_floats of the chain.
-extern "C" int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const float* const* packed, const float* const* bias, const float* x,
-                                  float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, hipStream_t stream) {
+// buf_a, buf_b: each at least the largest output of layers 0 .. n-2; ws: the largest mvs_conv2d_wide_workspace_floats[_arith] of the chain.
+// ... _arith: every layer in that arithmetic (packed[i]: mvs_conv2d_wide_pack_weights_arith with the same arith).
+extern "C" int mvs_conv_trunk_fwd_arith(int n, const MvsTrunkLayer* layers, const void* const* packed, const float* const* bias, const float* x,
+                                        float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, int arith, hipStream_t stream) {
+    C2W_REQUIRE_ARITH("conv_trunk_fwd", arith);
     MVS_REQUIRE(n >= 1 && n <= MVS_TRUNK_MAX_LAYERS, MVS_ERR_SHAPE, "conv_trunk_fwd: 1..%d layers, got %d", MVS_TRUNK_MAX_LAYERS, n);
     MVS_REQUIRE(layers && packed && bias && x && out && ws && (n == 1 || (buf_a && buf_b)), MVS_ERR_NULL, "conv_trunk_fwd: null pointer argument");
     MVS_REQUIRE(c2w_aligned(x) && c2w_aligned(buf_a) && c2w_aligned(buf_b) && c2w_aligned(ws) && c2w_aligned(out), MVS_ERR_UNSUPPORTED,
@@ -1504,10 +1569,14 @@ extern "C" int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const floa
     for (int i = 0; i < n; ++i) {
         const MvsTrunkLayer& l = layers[i];
         float* dst = i == n - 1 ? out : ((i & 1) ? buf_b : buf_a);
-        int rc = c2w_run(src, packed[i], bias[i], dst, ws, N, h, w, l.cin, l.cout, l.relu, l.pool_after, stream);
+        int rc = c2w_run(src, packed[i], bias[i], dst, ws, N, h, w, l.cin, l.cout, l.relu, l.pool_after, arith, stream);
         if (rc) return rc;
         if (l.pool_after) { h /= 2; w /= 2; }
         src = dst;
     }
     return MVS_OK;
+}
+extern "C" int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const float* const* packed, const float* const* bias, const float* x,
+                                  float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, hipStream_t stream) {
+    return mvs_conv_trunk_fwd_arith(n, layers, (const void* const*)packed, bias, x, buf_a, buf_b, ws, out, N, H, W, MVS_ARITH_F32, stream);
 }

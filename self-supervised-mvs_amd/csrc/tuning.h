@@ -58,7 +58,8 @@
     X(c2w_tile,         0,    0, 2,       "0 = t128x64 when its launch has at least c2w_big_min workgroups, else t64x64; 1 = always t64x64; 2 = always t128x64") \
     X(c2w_big_min,      512,  0, 1 << 30, "... workgroups (two per CU)") \
     X(c2w_splitk,       0,    0, 8,       "K ranges of a layer: 0 = doubled (<= 8) while a t64x64 launch has fewer than c2w_split_min workgroups, 1 = never split, 2..8 = this many") \
-    X(c2w_split_min,    512,  0, 1 << 30, "... workgroups (two per CU)")
+    X(c2w_split_min,    512,  0, 1 << 30, "... workgroups (two per CU)") \
+    X(c2w_bf_split_min, 2048, 0, 1 << 30, "c2w_split_min of the bf16 arms (arith = bf16): eight workgroups per CU")
 
 struct MvsTuning {
 #define MVS_KNOB_FIELD(key, def, lo, hi, doc) int key;

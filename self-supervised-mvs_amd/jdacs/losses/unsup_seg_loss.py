@@ -23,12 +23,12 @@ def compute_seg_loss(warped_seg, ref_seg, mask):
 
 
 class UnSupSegLoss(nn.Module):
-    def __init__(self, args_or_K, net=None, hip_features=None):
+    def __init__(self, args_or_K, net=None, hip_features=None, feature_arith="f32"):
         """args_or_K: the reference's ``args`` (its ``seg_clusters`` is used) or the number of clusters K; net: SegDFF's
-        feature extractor (None: the pretrained VGG19); hip_features: SegDFF's, passed through unchanged."""
+        feature extractor (None: the pretrained VGG19); hip_features, feature_arith: SegDFF's, passed through unchanged."""
         super().__init__()
         k = args_or_K if isinstance(args_or_K, int) else args_or_K.seg_clusters
-        self.seg_model = SegDFF(K=k, max_iter=50, net=net, hip_features=hip_features)
+        self.seg_model = SegDFF(K=k, max_iter=50, net=net, hip_features=hip_features, feature_arith=feature_arith)
 
     def forward(self, imgs, cams, depth):
         """imgs [B,N,3,H,W], cams [B,N,2,4,4] (intrinsics at the depth map's resolution), depth [B,h,w]."""

@@ -146,15 +146,21 @@ class SegDFF(nn.Module):
     features, one NMF problem per batch item (seg_dff.py:109-143).  net: the feature extractor (its ``.features`` is applied
     to the 224x224 images); None = torchvision's pretrained VGG19 without ``features['36']``, as in the reference.
     hip_features: False = the stock PyTorch call; True = the HIP trunk (raises when ``trunk_served(net)`` is false); None = the
-    HIP trunk when it is served, the images are on the GPU and HIP_FEATURES_DEFAULT says so."""
+    HIP trunk when it is served, the images are on the GPU and HIP_FEATURES_DEFAULT says so.
+    feature_arith: the arithmetic of the HIP trunk's multiplications (``ops.conv2d_wide_forward``): "f32" (default) or "bf16";
+    opt-in.  Anything but "f32" means the HIP trunk (as ``hip_features=True``: there is no such stock path), so it is
+    a ValueError together with ``hip_features=False`` or with a network the HIP trunk does not serve."""
 
     # what ``hip_features=None`` does with a served trunk on the GPU: set by the measurement of tools/vgg_features_bench.py
     # (profiles/vgg_features_timing.json) under the rule "HIP only when its p90 is below the stock path's p10": N = 7 on one
     # MI355X, HIP 3.088 ms (p90 3.104) against 3.182 ms (p10 3.168) for the stock path
     HIP_FEATURES_DEFAULT = True
 
-    def __init__(self, K, max_iter=50, net=None, hip_features=None):
+    def __init__(self, K, max_iter=50, net=None, hip_features=None, feature_arith="f32"):
         super().__init__()
+        ops.wide_arith(feature_arith)
+        if feature_arith not in (0, "f32") and hip_features is False:
+            raise ValueError("SegDFF(feature_arith=%r) is an arithmetic of the HIP trunk: it cannot go with hip_features=False" % (feature_arith,))
         self.K = K
         self.max_iter = max_iter
         if net is None:
@@ -170,7 +176,12 @@ class SegDFF(nn.Module):
         if hip_features and not trunk_served(net):
             raise ValueError("SegDFF(hip_features=True): net.features is not a trunk the HIP kernels serve (3x3 stride-1 pad-1 "
                              "convolutions with 3 or 32..512 -> 32..512 channels in steps of 32, ReLU, MaxPool2d(2, 2))")
+        if feature_arith not in (0, "f32"):
+            if not trunk_served(net):
+                raise ValueError("SegDFF(feature_arith=%r): net.features is not a trunk the HIP kernels serve" % (feature_arith,))
+            hip_features = True
         self.hip_features = hip_features
+        self.feature_arith = feature_arith
 
     def _hip_route(self, imgs):
         if self.hip_features is False:
@@ -191,7 +202,8 @@ class SegDFF(nn.Module):
         layers = self._hip_route(imgs)
         if layers is not None:
             x = ops.resize_bilinear_cl(x.float(), (224, 224))
-            plan = ops.trunk_plan([(m.weight, m.bias, relu, pool) for m, relu, pool in layers], x.shape, x)
+            plan = ops.trunk_plan([(m.weight, m.bias, relu, pool) for m, relu, pool in layers], x.shape, x,
+                                   arith=self.feature_arith)
             feats = ops.conv_trunk_forward(plan, x)                    # [N,h,w,C]: the NMF's layout already
             h, w, c = feats.shape[1:]
             return feats.view(b, nv * h * w, c), h, w

@@ -2318,9 +2318,21 @@ def conv2d_wide_serves(cin: int, cout: int) -> bool:
     return (cin == 3 or (32 <= cin <= 512 and cin % 32 == 0)) and 32 <= cout <= 512 and cout % 32 == 0
 
 
-def _wide_pack(lib, weight, like):
+WIDE_ARITH = {"f32": 0, "bf16": 2}     # include/mvs_hip.h: MVS_ARITH_*
+
+
+def wide_arith(arith):
+    """"f32" | "bf16" (or its MVS_ARITH_* number) -> the number; anything else is a ValueError"""
+    if isinstance(arith, str) and arith in WIDE_ARITH:
+        return WIDE_ARITH[arith]
+    if isinstance(arith, int) and not isinstance(arith, bool) and arith in WIDE_ARITH.values():
+        return arith
+    raise ValueError("conv2d_wide: arith must be one of %s, got %r" % (", ".join(repr(k) for k in WIDE_ARITH), arith))
+
+
+def _wide_pack(lib, weight, like, arith=0):
     cout, cin, kh, kw = weight.shape
-    nfl = lib.raw("mvs_conv2d_wide_packed_floats", cin, cout) if (kh, kw) == (3, 3) else -1
+    nfl = lib.raw("mvs_conv2d_wide_packed_bytes_arith", cin, cout, arith) // 4 if (kh, kw) == (3, 3) else -1
     if nfl < 0:
         raise ValueError("conv2d_wide: serves 3x3 layers with 3 or 32..512 input and 32..512 output channels in steps of 32, got "
                          "weight %s" % (tuple(weight.shape),))
@@ -2329,21 +2341,28 @@ def _wide_pack(lib, weight, like):
     if wl is None:
         w, wl = w.contiguous(), 0        # (kept in a local: the pointer must stay valid until the call has been made)
     packed = torch.empty(nfl, dtype=torch.float32, device=like.device)
-    lib.call("mvs_conv2d_wide_pack_weights", _p(w), _p(packed), cin, cout, wl, _stream(like), tag=("pack2d_wide:%d>%d", cin, cout))
+    if arith == 0:
+        lib.call("mvs_conv2d_wide_pack_weights", _p(w), _p(packed), cin, cout, wl, _stream(like), tag=("pack2d_wide:%d>%d", cin, cout))
+    else:
+        lib.call("mvs_conv2d_wide_pack_weights_arith", _p(w), _p(packed), cin, cout, wl, arith, _stream(like),
+                 tag=("pack2d_wide:%d>%d:a%d", cin, cout, arith))
     return packed
 
 
-def _wide_ws_floats(lib, n, h, w, cin, cout):
-    nfl = lib.raw("mvs_conv2d_wide_workspace_floats", n, h, w, cin, cout)
+def _wide_ws_floats(lib, n, h, w, cin, cout, arith=0):
+    nfl = lib.raw("mvs_conv2d_wide_workspace_floats_arith", n, h, w, cin, cout, arith)
     if nfl < 0:
         raise ValueError("conv2d_wide: unsupported shape N=%d H=%d W=%d Cin=%d Cout=%d" % (n, h, w, cin, cout))
     return int(nfl)
 
 
-def conv2d_wide_forward(x_cl, weight, bias=None, relu=False, pool=False):
+def conv2d_wide_forward(x_cl, weight, bias=None, relu=False, pool=False, arith="f32"):
     """x_cl [N,H,W,Cin] (contiguous), weight [Cout,Cin,3,3] (contiguous or channels-last in memory, read in place), bias [Cout] or
     None -> [relu](conv3x3(x, pad 1) + bias) as [N,H,W,Cout], or [N,H//2,W//2,Cout] with pool (2x2 max pool, stride 2, floor).
-    Forward only.  The weight image is packed by every call: a trunk packs once (conv_trunk_forward)."""
+    Forward only.  The weight image is packed by every call: a trunk packs once (conv_trunk_forward).
+    arith: "f32" (the fp32 MFMA) or "bf16" (the bf16 MFMA on operands rounded to nearest-even bf16); fp32 in, out and
+    accumulation in both (csrc/conv2d_wide_bf16_kernels.h)."""
+    arith = wide_arith(arith)
     lib = _lib_for(x_cl)
     _frozen("conv2d_wide_forward", x_cl, weight, bias)
     if x_cl.dim() != 4 or weight.dim() != 4 or weight.shape[1] != x_cl.shape[3]:
@@ -2353,14 +2372,18 @@ def conv2d_wide_forward(x_cl, weight, bias=None, relu=False, pool=False):
     x = x_cl.detach().contiguous()
     n, h, w, cin = x.shape
     cout = weight.shape[0]
-    packed = _wide_pack(lib, weight, x)
-    ws = torch.empty(_wide_ws_floats(lib, n, h, w, cin, cout), dtype=torch.float32, device=x.device)
+    packed = _wide_pack(lib, weight, x, arith)
+    ws = torch.empty(_wide_ws_floats(lib, n, h, w, cin, cout, arith), dtype=torch.float32, device=x.device)
     if pool and (h < 2 or w < 2):
         raise ValueError("conv2d_wide_forward: a %dx%d map cannot be pooled" % (h, w))
     y = torch.empty((n, h // 2, w // 2, cout) if pool else (n, h, w, cout), dtype=torch.float32, device=x.device)
     bias_c = None if bias is None else bias.detach().contiguous()
-    lib.call("mvs_conv2d_wide_fwd", _p(x), _p(packed), _p(bias_c), _p(y), _p(ws), n, h, w, cin, cout, int(bool(relu)), int(bool(pool)),
-             _stream(x), tag=("fwd2d_wide:%d>%d:%dx%dx%d", cin, cout, n, h, w))
+    if arith == 0:
+        lib.call("mvs_conv2d_wide_fwd", _p(x), _p(packed), _p(bias_c), _p(y), _p(ws), n, h, w, cin, cout, int(bool(relu)), int(bool(pool)),
+                 _stream(x), tag=("fwd2d_wide:%d>%d:%dx%dx%d", cin, cout, n, h, w))
+    else:
+        lib.call("mvs_conv2d_wide_fwd_arith", _p(x), _p(packed), _p(bias_c), _p(y), _p(ws), n, h, w, cin, cout, int(bool(relu)),
+                 int(bool(pool)), arith, _stream(x), tag=("fwd2d_wide:%d>%d:%dx%dx%d:a%d", cin, cout, n, h, w, arith))
     return y
 
 
@@ -2391,7 +2414,7 @@ def resize_bilinear_cl(x, size):
 
 
 _TRUNK_PLANS = {}
-_TRUNK_KNOBS = ("c2w_tile", "c2w_big_min", "c2w_splitk", "c2w_split_min")
+_TRUNK_KNOBS = ("c2w_tile", "c2w_big_min", "c2w_splitk", "c2w_split_min", "c2w_bf_split_min")
 
 
 class _TrunkPlan:
@@ -2399,8 +2422,9 @@ class _TrunkPlan:
     images (made once, here), the two ping-pong activation buffers and the workspace.  The buffers belong to the plan: two
     forwards of the same plan are ordered by the stream they are enqueued on."""
 
-    def __init__(self, lib, layers, xshape, like):
+    def __init__(self, lib, layers, xshape, like, arith=0):
         n, h, w, cin = xshape
+        self.arith = arith
         self.n_layers = len(layers)
         self.xshape = tuple(xshape)
         self.table = (_lib.MvsTrunkLayer * len(layers))()
@@ -2412,9 +2436,9 @@ class _TrunkPlan:
                 raise ValueError("conv_trunk: layer %d takes %d channels, its input has %d" % (i, cin_w, cin))
             t = self.table[i]
             t.cin, t.cout, t.relu, t.pool_after = cin, cout, int(bool(relu)), int(bool(pool))
-            self.packed.append(_wide_pack(lib, weight, like))
+            self.packed.append(_wide_pack(lib, weight, like, arith))
             self.bias.append(None if bias is None else bias.detach().contiguous().clone())
-            ws_floats = max(ws_floats, _wide_ws_floats(lib, n, h, w, cin, cout))
+            ws_floats = max(ws_floats, _wide_ws_floats(lib, n, h, w, cin, cout, arith))
             if pool:
                 if h < 2 or w < 2:
                     raise ValueError("conv_trunk: layer %d: a %dx%d map cannot be pooled" % (i, h, w))
@@ -2430,20 +2454,22 @@ class _TrunkPlan:
         self.ws = torch.empty(ws_floats, dtype=torch.float32, device=like.device)
 
 
-def trunk_plan(layers, xshape, like):
+def trunk_plan(layers, xshape, like, arith="f32"):
     """layers: [(weight [Cout,Cin,3,3], bias [Cout] or None, relu, pool_after)] of a frozen trunk; xshape (N,H,W,Cin).  The plan is
     cached on the input shape, the device and every parameter's data_ptr() and _version: a load_state_dict or any other in-place
-    edit of a parameter makes a new plan (and packs again); an unchanged trunk packs once."""
+    edit of a parameter makes a new plan (and packs again); an unchanged trunk packs once.  arith: as conv2d_wide_forward; it is
+    part of the cache key (the packed images depend on it): each arithmetic of one network has its own plan."""
+    arith = wide_arith(arith)
     lib = _lib_for(like)
     _frozen("conv_trunk_forward", *[t for l in layers for t in l[:2]])
-    key = (tuple(int(v) for v in xshape), str(like.device), tuple(lib.get_tuning(k) for k in _TRUNK_KNOBS),
+    key = (tuple(int(v) for v in xshape), str(like.device), arith, tuple(lib.get_tuning(k) for k in _TRUNK_KNOBS),
            tuple((wt.data_ptr(), wt._version, tuple(wt.shape), _w_layout(wt), None if b is None else (b.data_ptr(), b._version), bool(r), bool(p))
                  for wt, b, r, p in layers))
     plan = _TRUNK_PLANS.get(key)
     if plan is None:
         if len(_TRUNK_PLANS) >= 4:       # (a plan holds its activation buffers: a stale one is 100s of MB)
             _TRUNK_PLANS.clear()
-        plan = _TRUNK_PLANS[key] = _TrunkPlan(lib, layers, key[0], like)
+        plan = _TRUNK_PLANS[key] = _TrunkPlan(lib, layers, key[0], like, arith)
     return plan
 
 
@@ -2457,6 +2483,11 @@ def conv_trunk_forward(plan, x):
     x = x.detach().contiguous()
     out = torch.empty(plan.out_shape, dtype=torch.float32, device=x.device)
     n, h, w, _ = plan.xshape
-    lib.call("mvs_conv_trunk_fwd", plan.n_layers, plan.table, plan.packed_ptrs, plan.bias_ptrs, _p(x), _p(plan.buf_a), _p(plan.buf_b),
-             _p(plan.ws), _p(out), n, h, w, _stream(x), tag=("trunk_fwd:%d:%dx%dx%d", plan.n_layers, n, h, w))
+    if plan.arith == 0:
+        lib.call("mvs_conv_trunk_fwd", plan.n_layers, plan.table, plan.packed_ptrs, plan.bias_ptrs, _p(x), _p(plan.buf_a), _p(plan.buf_b),
+                 _p(plan.ws), _p(out), n, h, w, _stream(x), tag=("trunk_fwd:%d:%dx%dx%d", plan.n_layers, n, h, w))
+    else:
+        lib.call("mvs_conv_trunk_fwd_arith", plan.n_layers, plan.table, plan.packed_ptrs, plan.bias_ptrs, _p(x), _p(plan.buf_a),
+                 _p(plan.buf_b), _p(plan.ws), _p(out), n, h, w, plan.arith, _stream(x),
+                 tag=("trunk_fwd:%d:%dx%dx%d:a%d", plan.n_layers, n, h, w, plan.arith))
     return out
