@@ -229,6 +229,29 @@ int mvs_masked_smooth_l1_fwd(const float* est, const float* gt, const float* mas
 int mvs_masked_smooth_l1_bwd(const float* est, const float* gt, const float* mask, const float* fwd_out, const float* gloss,
                              long long n, float* gest, hipStream_t stream);
 
+/* ---- the seven depth-map validation metrics of one (est, gt, mask) triple (csrc/depth_metrics_kernels.h) -------------------------
+ * Replaces AbsDepthError_metrics and Thres_metrics with their per-image wrapper (jdacs/utils.py:134-163, the same text in
+ * jdacs-ms/utils.py) and non_zero_mean_absolute_diff / less_one_percentage / less_three_percentage (jdacs/losses/unsup_loss.py:
+ * 86-125, jdacs-ms/losses/unsup_loss.py:89-128) as train.py calls them in a block (jdacs/train.py:232-238, :319-325,
+ * jdacs-ms/train.py:271-277), and DictAverageMeter.update (jdacs/utils.py:112-131) for these values.
+ * est, gt [B,HW] fp32 (device).  mask [B,HW]: torch.bool bytes (mask_is_byte != 0, non-zero = selected) or fp32 (selected where
+ * > 0.5).  interval [B] fp32 (device) or NULL: then mae, less_one and less_three come out NaN.  thresholds: HOST array of T floats,
+ * 0 <= T <= 8 (copied into the launch; NULL allowed for T = 0).
+ * out [4+T] (device): abs error, the T rates of |est - gt| > threshold (strict), mae, less_one, less_three.  per_image [B,2+T]: abs
+ * error and the T rates of every image, then the image's term of mae.  Abs error and rates are means over the image's mask, then
+ * the mean over images (an empty mask: NaN); mae is the SUM over images of (sum |[gt != 0] (gt - est)| / interval_b) / (count_b +
+ * 1e-7); less_k = sum [gt != 0][|gt - est| / interval_b <= k] / (sum [gt != 0] + 1e-7) over the whole batch.  NaN inputs fall where
+ * the reference's comparisons put them.  Counts are exact integers, turned into fp32 once at the division: equal to the reference's
+ * fp32 sums of ones below 2^24 pixels per image (per batch for less_k).
+ * meter / meter_count (both or neither): fp64 [4+T] running sums to which out is added, and one 64-bit call counter.
+ * ws: mvs_depth_metrics_workspace_bytes() bytes = B * ceil(HW / 4096) tile records of 64 bytes; the query answers -1 for B outside
+ * 1..65535, HW < 1 or T outside 0..8.  Two launches, no atomics, no host synchronisation; the same bits on every run and for
+ * either mask type. */
+long long mvs_depth_metrics_workspace_bytes(int B, int HW, int T);
+int mvs_depth_metrics(const float* est, const float* gt, const void* mask, int mask_is_byte, const float* interval,
+                      const float* thresholds, int T, int B, int HW, void* ws, float* out, float* per_image, double* meter,
+                      long long* meter_count, hipStream_t stream);
+
 /* ---- K9/K10: softmax over depth + soft-argmin regression + photometric confidence --------------
  * Replace F.softmax(dim=1) + depth_regression + the pad/avg_pool3d/gather confidence:
  *   jdacs/models/mvsnet.py:141-151, jdacs/models/module.py:145-148;

@@ -61,3 +61,5 @@ extern "C" int mvs_masked_smooth_l1_bwd(const float* est, const float* gt, const
     MVS_LAUNCH(masked_smooth_l1_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, est, gt, mask, fwd_out, gloss, n, gest);
     return mvs_check_launch("masked_smooth_l1_bwd");
 }
+
+#include "depth_metrics_kernels.h"   // the seven validation metrics of the same (est, gt, mask) maps: mvs_depth_metrics

@@ -37,3 +37,25 @@ class UnSupLoss(nn.Module):
         self.reconstr_loss, self.ssim_loss, self.smooth_loss = reconstr, ssim, smooth
         self.unsup_loss = total
         return total
+
+
+def _interval_metrics(y_true, y_pred, interval):
+    # y_true doubles as the (ignored) fp32 mask: these three values depend on [gt != 0] only
+    y_true, y_pred = y_true.float(), y_pred.float()
+    return ops.depth_metrics(y_pred, y_true, y_true, interval, ())[0]
+
+
+def non_zero_mean_absolute_diff(y_true, y_pred, interval):
+    """jdacs/losses/unsup_loss.py:86-95: the SUM over the batch of (sum |[gt != 0] (gt - est)| / interval_b) / (count_b + 1e-7).
+    y_true, y_pred [B,H,W], interval [B]; 0-dim device tensor from one ops.depth_metrics call (csrc/depth_metrics_kernels.h)."""
+    return _interval_metrics(y_true, y_pred, interval)[1]
+
+
+def less_one_percentage(y_true, y_pred, interval):
+    """jdacs/losses/unsup_loss.py:98-111: share of the batch's gt != 0 pixels with |gt - est| / interval_b <= 1."""
+    return _interval_metrics(y_true, y_pred, interval)[2]
+
+
+def less_three_percentage(y_true, y_pred, interval):
+    """jdacs/losses/unsup_loss.py:114-125: the same with <= 3."""
+    return _interval_metrics(y_true, y_pred, interval)[3]

@@ -1,11 +1,18 @@
 """Caller-side helpers of the path (jdacs/utils.py:36-76, jdacs/eval.py:125-165): recursive
 tensor -> numpy conversion, checkpoint loading with the ``module.`` prefix DataParallel leaves, and writing the depth /
-confidence maps as PFM files.  Device-agnostic: nothing here hard-codes ``.cuda()``."""
+confidence maps as PFM files.  Device-agnostic: nothing here hard-codes ``.cuda()``.
+
+The depth-map metrics of the training scripts' detailed summary (jdacs/utils.py:112-163, called at jdacs/train.py:232-238 and
+:319-325) under the reference's names -- ``Thres_metrics``, ``AbsDepthError_metrics``, ``compute_metrics_for_each_image``,
+``make_nograd_func``, ``DictAverageMeter`` -- each metric one ``ops.depth_metrics`` call (two HIP launches, no host
+synchronisation, csrc/depth_metrics_kernels.h) that returns a 0-dim device tensor; ``depth_metrics`` gives all seven values of
+that block from ONE call, and ``DepthMetricsMeter`` averages them over the validation set on the device."""
 import os
 
 import numpy as np
 import torch
 
+from .. import ops
 from .datasets.data_io import save_pfm
 
 
@@ -76,3 +83,91 @@ def save_depth_outputs(outputs, filenames, outdir, depth_png=False):
                 write_depth_img(path + ".png", np.ascontiguousarray(arr, dtype=np.float32))
                 written.append(path + ".png")
     return written
+
+
+def make_nograd_func(func):
+    """jdacs/utils.py:24-31: ``func`` run under torch.no_grad()"""
+    def wrapper(*f_args, **f_kwargs):
+        with torch.no_grad():
+            return func(*f_args, **f_kwargs)
+    return wrapper
+
+
+def compute_metrics_for_each_image(metric_func):
+    """jdacs/utils.py:134-145, for a caller's OWN metric: ``metric_func(est_i, gt_i, mask_i, *args)`` per batch item, then the mean
+    of the stacked results.  The metrics of this module do not go through it: the kernel forms the per-image means itself."""
+    def wrapper(depth_est, depth_gt, mask, *args):
+        results = [metric_func(depth_est[i], depth_gt[i], mask[i], *args) for i in range(depth_gt.shape[0])]
+        return torch.stack(results).mean()
+    return wrapper
+
+
+def Thres_metrics(depth_est, depth_gt, mask, thres):
+    """jdacs/utils.py:148-155: per image the share of mask pixels with |est - gt| > thres (strict), then the mean over images.
+    mask: bool (``mask > 0.5`` as train.py passes it) or the fp32 mask itself.  0-dim device tensor, not read back."""
+    assert isinstance(thres, (int, float))
+    return ops.depth_metrics(depth_est, depth_gt, mask, None, (thres,))[0][1]
+
+
+def AbsDepthError_metrics(depth_est, depth_gt, mask):
+    """jdacs/utils.py:158-163: per image the mean |est - gt| over the mask, then the mean over images (the "abs-depth L1" of
+    BASELINE.md).  Not differentiable, like the reference's (make_nograd_func)."""
+    return ops.depth_metrics(depth_est, depth_gt, mask, None, ())[0][0]
+
+
+METRIC_KEYS = ("abs_depth_error", "thres2mm_error", "thres4mm_error", "thres8mm_error", "mae", "less_one_accuracy",
+               "less_three_accuracy")
+
+
+def depth_metrics(depth_est, depth_gt, mask, depth_interval):
+    """The seven scalar_outputs of jdacs/train.py:232-238 (jdacs-ms/train.py:271-277) as a dict of 0-dim device tensors, from one
+    launch pair.  mask: train.py's fp32 mask or ``mask > 0.5``."""
+    out = ops.depth_metrics(depth_est, depth_gt, mask, depth_interval, (2, 4, 8))[0]
+    return {k: out[i] for i, k in enumerate(METRIC_KEYS)}
+
+
+class DepthMetricsMeter(object):
+    """DictAverageMeter for the seven metrics without ``tensor2float``: ``update`` adds the call's values into fp64 sums ON THE
+    DEVICE (the finish kernel does it) and never synchronises; ``mean()`` reads the sums back -- the one synchronisation of a
+    validation pass -- and returns the keys DictAverageMeter.mean() would."""
+
+    def __init__(self):
+        self._buf = None                # float64 [8]: seven sums, then the update count as int64 bits
+
+    def update(self, depth_est, depth_gt, mask, depth_interval):
+        n = len(METRIC_KEYS)
+        if self._buf is None:
+            self._buf = torch.zeros(n + 1, dtype=torch.float64, device=depth_est.device)
+        out = ops.depth_metrics(depth_est, depth_gt, mask, depth_interval, (2, 4, 8),
+                                meter=(self._buf[:n], self._buf[n:].view(torch.int64)))[0]
+        return {k: out[i] for i, k in enumerate(METRIC_KEYS)}
+
+    @property
+    def count(self):
+        return 0 if self._buf is None else int(self._buf.cpu()[len(METRIC_KEYS):].view(torch.int64))
+
+    def mean(self):
+        if self._buf is None:
+            raise RuntimeError("DepthMetricsMeter.mean() before any update()")
+        host = self._buf.cpu()
+        n = len(METRIC_KEYS)
+        count = int(host[n:].view(torch.int64))
+        return {k: float(host[i]) / count for i, k in enumerate(METRIC_KEYS)}
+
+
+class DictAverageMeter(object):
+    """jdacs/utils.py:112-131: running sums of dicts of Python floats (what ``tensor2float`` returns)."""
+
+    def __init__(self):
+        self.data = {}
+        self.count = 0
+
+    def update(self, new_input):
+        self.count += 1
+        for k, v in new_input.items():
+            if not isinstance(v, float):
+                raise NotImplementedError("invalid data {}: {}".format(k, type(v)))
+            self.data[k] = self.data.get(k, 0.0) + v
+
+    def mean(self):
+        return {k: v / self.count for k, v in self.data.items()}

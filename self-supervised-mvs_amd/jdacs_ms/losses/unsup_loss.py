@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
+from ...jdacs.losses.unsup_loss import less_one_percentage, less_three_percentage, non_zero_mean_absolute_diff  # noqa: F401  (:89-128, the same text as jdacs)
 
 
 class UnSupLoss(nn.Module):

@@ -2026,6 +2026,54 @@ def seg_loss(depth, ref_seg, view_segs, kinv, proj):
 
 
 # ------------------------------------------------------------------------------------------------
+# The seven depth-map validation metrics of train.py's detailed summary (csrc/depth_metrics_kernels.h)
+# ------------------------------------------------------------------------------------------------
+def depth_metrics(est, gt, mask, interval=None, thresholds=(2, 4, 8), meter=None):
+    """est, gt [B,H,W] fp32; mask [B,H,W] torch.bool (or uint8) or fp32 (selected where > 0.5); interval [B] (any shape with B
+    entries) or None; thresholds: up to 8 Python numbers.  Returns (out [4+T], per_image [B,2+T]) device tensors:
+    out = abs error, the T rates of |est - gt| > threshold, mae, less_one, less_three (jdacs/utils.py:134-163,
+    jdacs/losses/unsup_loss.py:86-125; the last three NaN without an interval); per_image = abs error and the T rates of every
+    image, then its term of mae.  meter: (sums float64 [4+T], count int64 [1]) device tensors to which this call's out is added
+    and whose count is incremented, on the device.  One mvs_depth_metrics call = two launches; nothing here synchronises."""
+    lib = _lib_for(est)
+    _lib_for(gt)
+    if est.dim() < 2 or est.shape != gt.shape or est.shape != mask.shape:
+        raise ValueError("depth_metrics: est, gt and mask must share one [B,H,W] shape, got %s %s %s"
+                         % (tuple(est.shape), tuple(gt.shape), tuple(mask.shape)))
+    if mask.device != est.device or gt.device != est.device:
+        raise ValueError("depth_metrics: est, gt and mask must be on one device, got %s %s %s" % (est.device, gt.device, mask.device))
+    if mask.dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise TypeError("depth_metrics: mask must be torch.bool / uint8 or float32, got %s" % mask.dtype)
+    thresholds = [float(t) for t in thresholds]
+    T = len(thresholds)
+    b = est.shape[0]
+    hw = est.numel() // b if b else 0
+    nbytes = lib.raw("mvs_depth_metrics_workspace_bytes", b, hw, T)
+    if nbytes < 0:
+        raise ValueError("depth_metrics: unsupported sizes B=%d HW=%d T=%d (1 <= B <= 65535, HW >= 1, 0 <= T <= 8 thresholds)" % (b, hw, T))
+    with torch.no_grad():
+        est, gt, mask = est.detach().contiguous(), gt.detach().contiguous(), mask.detach().contiguous()
+        if interval is not None:
+            if interval.numel() != b or interval.device != est.device:
+                raise ValueError("depth_metrics: interval must hold B = %d values on %s, got %s on %s"
+                                 % (b, est.device, tuple(interval.shape), interval.device))
+            interval = interval.detach().reshape(b).to(torch.float32).contiguous()
+        m_sum = m_cnt = None
+        if meter is not None:
+            m_sum, m_cnt = meter
+            if m_sum.dtype != torch.float64 or m_sum.numel() != 4 + T or m_cnt.dtype != torch.int64 or m_cnt.numel() != 1 or \
+                    not m_sum.is_contiguous() or m_sum.device != est.device or m_cnt.device != est.device:
+                raise ValueError("depth_metrics: meter must be (float64 [%d], int64 [1]) contiguous tensors on %s" % (4 + T, est.device))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=est.device)
+        out = torch.empty(4 + T, dtype=torch.float32, device=est.device)
+        per_image = torch.empty((b, 2 + T), dtype=torch.float32, device=est.device)
+        th = (C.c_float * max(T, 1))(*thresholds)
+        lib.call("mvs_depth_metrics", _p(est), _p(gt), _p(mask), 0 if mask.dtype == torch.float32 else 1, _p(interval), th, T, b, hw,
+                 _p(ws), _p(out), _p(per_image), _p(m_sum), _p(m_cnt), _stream(est))
+    return out, per_image
+
+
+# ------------------------------------------------------------------------------------------------
 # SURVEY 8(f)-2: per-level depth hypotheses of CVP-MVSNet
 # ------------------------------------------------------------------------------------------------
 def depth_hypotheses(ref_depths: torch.Tensor, mats: torch.Tensor) -> torch.Tensor:
