@@ -252,6 +252,34 @@ int mvs_depth_metrics(const float* est, const float* gt, const void* mask, int m
                       const float* thresholds, int T, int B, int HW, void* ws, float* out, float* per_image, double* meter,
                       long long* meter_count, hipStream_t stream);
 
+/* ---- training-sample preparation: the step's image tensors from the decoded 8-bit views (csrc/sample_prep_kernels.h) ------------
+ * Replaces, per view, center_image (jdacs/datasets/dtu_yao.py:94-99, jdacs-ms/dataset/dtu.py:112-119), transform_aug + x255 +
+ * center_image (dtu_yao.py:59-63, 241-247, 279-281; dtu.py:80-84, 164-166, 207-219), transform_seg (dtu_yao.py:64-67, 237-239;
+ * dtu.py:85-86, 160-162), random_image_mask on the reference view with the mask's F.interpolate(scale_factor=0.25) (jdacs/train.py:
+ * 269-275), and the transform chain of Augmentor (jdacs/models/augmentations.py:20-104).
+ * src (device), M views: src_kind 0 = u8 [M,H,W,3] as decoded, src_kind 1 = fp32 [M,3,H,W] in [0,1], quantised on load as ToPILImage
+ * does (x255, truncated).  src_image_stride: elements between two views (0 = 3 H W), so a row-prefix crop needs no copy.
+ * params: HOST fp32 [M,9] or NULL (then imgs_aug must be NULL): four operation ids in application order (0 brightness, 1 contrast,
+ * 2 saturation, 3 hue, -1 none; each at most once), their four factors, gamma (> 0).  rect: HOST int [M,4] (y, x, fh, fw) or NULL:
+ * the window of random_image_mask, fh = 0 for none.  Both are checked and copied into the launches' arguments.
+ * Arithmetic, fp32 on values in [0,1]: gray = 0.299 r + 0.587 g + 0.114 b; brightness clamp(f x); contrast clamp(f x + (1 - f)
+ * mean_HW(gray of the image as it stands)); saturation clamp(f x + (1 - f) gray); hue through hsv with colorsys's conventions,
+ * h = (h + f) mod 1; gamma clamp(x^gamma); all clamps to [0,1].  center_image: per channel (x - mean) / (sqrt(var) + 1e-8) with
+ * the population mean and variance over H W, from exact integer sums (imgs) or fp64 sums (imgs_aug), evaluated in fp64 and
+ * rounded once.
+ * Outputs (device, each may be NULL, not all): imgs = center_image(u8); imgs_aug = the chain, then x255 and center_image when
+ * aug_center != 0 (the loaders' form) or left in [0,1] (Augmentor's), then times the window mask; imgs_seg = (u8 / 255 - mean_c) /
+ * std_c with the ImageNet constants; all three logically [M,3,H,W], stored as such or as [M,H,W,3] when channels_last != 0.
+ * filter_mask [M, H / s, W / s] fp32 for s = mask_scale in {1, 4}: the mask's value at pixel (s i, s j), sizes floored.
+ * ws: mvs_sample_prep_workspace_bytes() bytes = M * ceil(H W / 4096) tile records of 128 bytes; the query answers -1 for M, H or
+ * W < 1 or M H W 3 >= 2^31.  Three launches per 64 views (two when imgs_aug is absent or not centred), no atomics, no host
+ * synchronisation, the same bits on every run.  Bad sizes, a null workspace or a bad operation id return a negative code and
+ * launch nothing. */
+long long mvs_sample_prep_workspace_bytes(int M, int H, int W);
+int mvs_sample_prep(const void* src, int src_kind, long long src_image_stride, const float* params, const int* rect, float* imgs,
+                    float* imgs_aug, float* imgs_seg, float* filter_mask, int mask_scale, int aug_center, int channels_last, int M,
+                    int H, int W, void* ws, hipStream_t stream);
+
 /* ---- K9/K10: softmax over depth + soft-argmin regression + photometric confidence --------------
  * Replace F.softmax(dim=1) + depth_regression + the pad/avg_pool3d/gather confidence:
  *   jdacs/models/mvsnet.py:141-151, jdacs/models/module.py:145-148;

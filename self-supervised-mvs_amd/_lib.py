@@ -87,6 +87,8 @@ SIGNATURES = {
     "mvs_masked_smooth_l1_bwd": (_i, [_f, _f, _f, _f, _f, _ll, _f, _s]),
     "mvs_depth_metrics_workspace_bytes": (_ll, [_i, _i, _i]),
     "mvs_depth_metrics": (_i, [_f, _f, _f, _i, _f, C.POINTER(_fl), _i, _i, _i, _f, _f, _f, _f, _f, _s]),
+    "mvs_sample_prep_workspace_bytes": (_ll, [_i, _i, _i]),
+    "mvs_sample_prep": (_i, [_f, _i, _ll, C.POINTER(_fl), C.POINTER(_i), _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _s]),
     "mvs_softargmin_conf_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _s]),
     "mvs_softargmin_conf_bwd": (_i, [_f, _f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _f, _s]),
     "mvs_conv2d_workspace_floats": (_ll, [_i] * 8),

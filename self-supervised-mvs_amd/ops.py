@@ -11,6 +11,7 @@ import ctypes as C
 import os
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -2071,6 +2072,81 @@ def depth_metrics(est, gt, mask, interval=None, thresholds=(2, 4, 8), meter=None
         lib.call("mvs_depth_metrics", _p(est), _p(gt), _p(mask), 0 if mask.dtype == torch.float32 else 1, _p(interval), th, T, b, hw,
                  _p(ws), _p(out), _p(per_image), _p(m_sum), _p(m_cnt), _stream(est))
     return out, per_image
+
+
+# ------------------------------------------------------------------------------------------------
+# Training-sample preparation: the step's image tensors from the decoded u8 views (csrc/sample_prep_kernels.h)
+# ------------------------------------------------------------------------------------------------
+def sample_prep(src, table=None, rects=None, imgs=True, seg=True, mask_scale=None, aug_center=True, channels_last=False):
+    """src: the M views, uint8 [M,H,W,3] as decoded (a row-prefix crop ``views[:, :rows]`` is read in place through the image
+    stride) or fp32 [M,3,H,W] in [0,1] (quantised on load as ToPILImage does).  table: HOST fp32 [M,9] (numpy array or CPU tensor)
+    -- four operation ids in application order (0 brightness, 1 contrast, 2 saturation, 3 hue, -1 none), their factors, gamma --
+    or None for no ``imgs_aug``.  rects: HOST int [M,4] (y, x, fh, fw) windows of random_image_mask, fh = 0 for none, or None.
+    mask_scale: None for no ``filter_mask``, 1, or 4 (= F.interpolate(mask, scale_factor=0.25)).  aug_center: x255 and
+    center_image after the gamma (the loaders' form); False leaves ``imgs_aug`` in [0,1] (Augmentor's form).
+    Returns a dict of the requested device tensors: "imgs", "imgs_aug", "imgs_seg" [M,3,H,W] (channels_last: the same logical
+    shape over [M,H,W,3] memory) and "filter_mask" [M,H//s,W//s].  One mvs_sample_prep call = three launches (two without a
+    centred imgs_aug); nothing here synchronises."""
+    lib = _lib.get()
+    if src.device.type != lib.device_type:
+        raise RuntimeError("mvs_amd: tensor on %s but the HIP library serves '%s' devices; the hot path has no "
+                           "CPU fallback" % (src.device, lib.device_type))
+    if src.dtype == torch.uint8:
+        if src.dim() != 4 or src.shape[3] != 3:
+            raise ValueError("sample_prep: uint8 views must be [M,H,W,3], got %s" % (tuple(src.shape),))
+        kind, (M, H, W) = 0, src.shape[:3]
+    elif src.dtype == torch.float32:
+        if src.dim() != 4 or src.shape[1] != 3:
+            raise ValueError("sample_prep: fp32 views must be [M,3,H,W], got %s" % (tuple(src.shape),))
+        kind, M, (H, W) = 1, src.shape[0], src.shape[2:]
+    else:
+        raise TypeError("sample_prep: views must be uint8 [M,H,W,3] or float32 [M,3,H,W], got %s" % src.dtype)
+    M, H, W = int(M), int(H), int(W)
+    nbytes = lib.raw("mvs_sample_prep_workspace_bytes", M, H, W)
+    if nbytes < 0:
+        raise ValueError("sample_prep: unsupported sizes M=%d H=%d W=%d (each >= 1, M H W 3 < 2^31)" % (M, H, W))
+    if mask_scale not in (None, 1, 4):
+        raise ValueError("sample_prep: mask_scale must be None, 1 or 4, got %r" % (mask_scale,))
+    if table is None and not imgs and not seg and mask_scale is None:
+        raise ValueError("sample_prep: no output requested")
+
+    def host(a, dtype, cols, what):
+        a = np.ascontiguousarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=dtype)
+        if a.shape != (M, cols):
+            raise ValueError("sample_prep: %s must be [M = %d, %d], got %s" % (what, M, cols, a.shape))
+        return a
+    with torch.no_grad():
+        src = src.detach()
+        inner = src[0]
+        if M > 1 and not (inner.is_contiguous() and src.stride(0) >= 3 * H * W):
+            src = src.contiguous()
+        elif M == 1 and not inner.is_contiguous():
+            src = src.contiguous()
+        stride = src.stride(0) if M > 1 else 3 * H * W
+        tab = None if table is None else host(table, np.float32, 9, "table")
+        rec = None if rects is None else host(rects, np.int32, 4, "rects")
+        dev = src.device
+
+        def image():
+            if channels_last:
+                return torch.empty((M, H, W, 3), dtype=torch.float32, device=dev).permute(0, 3, 1, 2)
+            return torch.empty((M, 3, H, W), dtype=torch.float32, device=dev)
+        out = {}
+        if imgs:
+            out["imgs"] = image()
+        if tab is not None:
+            out["imgs_aug"] = image()
+        if seg:
+            out["imgs_seg"] = image()
+        if mask_scale is not None:
+            out["filter_mask"] = torch.empty((M, H // mask_scale, W // mask_scale), dtype=torch.float32, device=dev)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        lib.call("mvs_sample_prep", _p(src), kind, stride,
+                 None if tab is None else tab.ctypes.data_as(C.POINTER(C.c_float)),
+                 None if rec is None else rec.ctypes.data_as(C.POINTER(C.c_int)),
+                 _p(out.get("imgs")), _p(out.get("imgs_aug")), _p(out.get("imgs_seg")), _p(out.get("filter_mask")),
+                 mask_scale or 1, 1 if aug_center else 0, 1 if channels_last else 0, M, H, W, _p(ws), _stream(src))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------
