@@ -221,6 +221,18 @@ int mvs_bn_eval_affine(const float* gamma, const float* beta, const float* runni
 /* y = relu?(x*scale+shift) (+ skip) */
 int mvs_bn_relu_fwd(const float* x, const float* scale, const float* shift, const float* skip, int relu, long long V,
                     int C, float* y, hipStream_t stream);
+/* Frozen statistics with a gradient: nn.BatchNorm2d / nn.BatchNorm3d in .eval() inside a model that trains (module.py:15-22,35-42
+ * under model.train() + bn.eval(), or model.eval() with autograd on).  stats [4][C] = running_mean, invstd = 1/sqrt(running_var +
+ * eps), scale = gamma/sqrt(running_var + eps), shift = beta - running_mean*scale: the layout of the train-mode stats, so the
+ * bn_raw epilogues of mvs_conv3d_dgrad / mvs_convT3d_dgrad take it as it is.  Forward: mvs_bn_relu_fwd with rows 2 and 3. */
+int mvs_bn_frozen_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps,
+                        int C, float* stats, hipStream_t stream);
+/* draw [V][C] = scale * dyh, dyh = dy * [raw*scale + shift > 0] (relu); dbeta = sum dyh, dgamma = sum dyh * (raw - running_mean) *
+ * invstd through fp64 slot rows [nslots][2][C].  dgamma == dbeta == NULL: one launch, no reduction, slots unused.  have_sums != 0:
+ * the slots already hold the two sums (an input-gradient epilogue was given `stats`): one launch.  have_sums == 0: caller-zeroed
+ * rows, filled by the pass and finished by a one-workgroup launch.  The running statistics are never written. */
+int mvs_bn_relu_bwd_frozen(const float* dy, const float* raw, const float* stats, double* slots, int nslots, int have_sums,
+                           int relu, long long V, int C, float* draw, float* dgamma, float* dbeta, hipStream_t stream);
 
 /* ---- mvsnet_loss (jdacs/models/mvsnet.py:164-166): mean smooth-L1 (beta 1) of est - gt over the n pixels with mask > 0.5 ----
  * forward: out[0] = loss (nan for an empty mask, like the reference's mean over an empty selection), out[1] = pixel count;

@@ -83,6 +83,8 @@ SIGNATURES = {
     "mvs_bn_relu_bwd_slots": (_i, [_f, _f, _f, _f, _i, _i, _i, _ll, _i, _f, _f, _f, _s]),
     "mvs_bn_eval_affine": (_i, [_f, _f, _f, _f, _fl, _i, _f, _f, _s]),
     "mvs_bn_relu_fwd": (_i, [_f, _f, _f, _f, _i, _ll, _i, _f, _s]),
+    "mvs_bn_frozen_stats": (_i, [_f, _f, _f, _f, _fl, _i, _f, _s]),
+    "mvs_bn_relu_bwd_frozen": (_i, [_f, _f, _f, _f, _i, _i, _i, _ll, _i, _f, _f, _f, _s]),
     "mvs_masked_smooth_l1_fwd": (_i, [_f, _f, _f, _ll, _f, _s]),
     "mvs_masked_smooth_l1_bwd": (_i, [_f, _f, _f, _f, _f, _ll, _f, _s]),
     "mvs_depth_metrics_workspace_bytes": (_ll, [_i, _i, _i]),

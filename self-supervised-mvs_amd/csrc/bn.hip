@@ -16,6 +16,11 @@
 // of the input-gradient kernel that produced dy (conv3d.hip, "bn_raw") or from bn_bwd_reduce_slots_kernel -- and the apply
 // kernel finishes them in its prologue (dgamma / dbeta written by workgroup (0, 0)).
 // Eval mode: scale/shift come from the running statistics (bn_eval_affine) and are applied inside the convolution epilogue.
+// Frozen statistics WITH a gradient (bn.training == False, autograd on: fine-tuning a checkpoint with its BatchNorm frozen): the
+// running statistics are constants, so stats [4][C] = (running_mean, invstd, scale, shift) is a pure function of the parameters
+// (bn_frozen_stats_kernel), the forward is raw -> bn_apply_relu_kernel, and the backward is ONE pass draw = scale * dyh with no mean
+// terms (bn_frozen_bwd_kernel); dbeta = sum dyh and dgamma = sum dyh*xhat are the very sums the train-mode slots carry, so an
+// input-gradient epilogue handed the frozen stats delivers them as before.  Nothing writes the running statistics.
 #include "mvs_rt.h"
 
 __device__ __forceinline__ float4 ld4g(const float* p) { return *reinterpret_cast<const float4*>(p); }
@@ -254,6 +259,81 @@ __global__ __launch_bounds__(256) void bn_bwd_slots_kernel(const float* __restri
     }
 }
 
+// ---- frozen statistics -------------------------------------------------------------------------------------------------
+// stats [4][C] = (running_mean, invstd, scale, shift): bn_eval_affine_kernel's scale / shift (same expressions, so the forward is
+// today's eval path bit for bit) plus the two rows the backward kernels and the bn_raw epilogues read.
+__global__ void bn_frozen_stats_kernel(const float* gamma, const float* beta, const float* rm, const float* rv, float eps, int C,
+                                       float* stats) {
+    int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < C) {
+        const float sd = sqrtf(rv[c] + eps);
+        const float sc = gamma[c] / sd;
+        stats[c] = rm[c];
+        stats[C + c] = 1.0f / sd;
+        stats[2 * C + c] = sc;
+        stats[3 * C + c] = beta[c] - rm[c] * sc;
+    }
+}
+
+// Frozen backward apply: draw = scale * dyh, dyh = dy * [raw*scale + shift > 0] (relu) -- two reads, one write per element.
+// MODE 0: nothing else (no affine gradient wanted, or a finishing launch follows).
+// MODE 1: the pass also adds its per-workgroup (sum dyh, sum dyh*xhat) into the caller-zeroed slot rows (bn_frozen_finish_kernel
+//         then writes dgamma / dbeta).
+// MODE 2: the sums are in the slots already (an input-gradient epilogue was given the frozen stats): workgroup 0 finishes
+//         dgamma / dbeta in its prologue, like the owner branch of bn_bwd_slots_kernel; the elementwise pass needs neither.
+template <int MODE>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                            const float* __restrict__ stats, double* __restrict__ slots, int nslots,
+                                                            size_t n4, int C, int relu, float* __restrict__ dx, float* dgamma,
+                                                            float* dbeta) {
+    __shared__ double red[MODE == 2 ? 256 : 1];
+    __shared__ double tot[MODE == 2 ? 128 : 1];
+    __shared__ float redf[MODE == 1 ? 256 * 8 : 1];
+    const int tid = threadIdx.x;
+    if (MODE == 2 && blockIdx.x == 0) {
+        bn_slot_totals(slots, nslots, C, red, tot);
+        if (tid < C) {
+            if (dbeta) dbeta[tid] = (float)tot[tid];
+            if (dgamma) dgamma[tid] = (float)tot[C + tid];
+        }
+    }
+    const int cq = C / 4;
+    const int c = (tid % cq) * 4;                       // the same channel quad on every grid-stride step (256 % cq == 0)
+    const float4 mu = ld4g(stats + c), is = ld4g(stats + C + c), sc = ld4g(stats + 2 * C + c), sh = ld4g(stats + 3 * C + c);
+    float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (size_t i = (size_t)blockIdx.x * 256 + tid; i < n4; i += (size_t)gridDim.x * 256) {
+        const float4 xv = ld4g(x + i * 4);
+        float4 g = ld4g(dy + i * 4);
+        if (relu) {
+            if (!(xv.x * sc.x + sh.x > 0.f)) g.x = 0.f;
+            if (!(xv.y * sc.y + sh.y > 0.f)) g.y = 0.f;
+            if (!(xv.z * sc.z + sh.z > 0.f)) g.z = 0.f;
+            if (!(xv.w * sc.w + sh.w > 0.f)) g.w = 0.f;
+        }
+        if (MODE == 1) {
+            v[0] += g.x; v[1] += g.y; v[2] += g.z; v[3] += g.w;
+            v[4] += g.x * ((xv.x - mu.x) * is.x); v[5] += g.y * ((xv.y - mu.y) * is.y);
+            v[6] += g.z * ((xv.z - mu.z) * is.z); v[7] += g.w * ((xv.w - mu.w) * is.w);
+        }
+        float4 o;
+        o.x = sc.x * g.x; o.y = sc.y * g.y; o.z = sc.z * g.z; o.w = sc.w * g.w;
+        *reinterpret_cast<float4*>(dx + i * 4) = o;
+    }
+    if (MODE == 1) bn_block_to_slot(v, redf, C, slots + (size_t)(blockIdx.x & (nslots - 1)) * 2 * C);
+}
+
+// one workgroup: dgamma / dbeta from the slot rows the MODE 1 pass filled
+__global__ __launch_bounds__(256) void bn_frozen_finish_kernel(const double* __restrict__ slots, int nslots, int C, float* dgamma,
+                                                               float* dbeta) {
+    __shared__ double red[256];
+    __shared__ double tot[128];
+    bn_slot_totals(slots, nslots, C, red, tot);
+    if ((int)threadIdx.x < C) {
+        if (dbeta) dbeta[threadIdx.x] = (float)tot[threadIdx.x];
+        if (dgamma) dgamma[threadIdx.x] = (float)tot[C + threadIdx.x];
+    }
+}
+
 static bool bn_c_ok(int C) { return C == 4 || C == 8 || C == 16 || C == 32 || C == 64; }
 static bool bn_slots_ok(int n) { return n >= 1 && n <= 256 && (n & (n - 1)) == 0; }
 static int ew_grid(size_t n4) {
@@ -350,3 +430,43 @@ extern "C" int mvs_bn_relu_fwd(const float* x, const float* scale, const float* 
     return mvs_check_launch("bn_relu_fwd");
 }
 
+// ---- frozen statistics (bn.training == False) with a gradient: module.py:15-22,35-42 under model.train() + bn.eval() ----
+extern "C" int mvs_bn_frozen_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                                   float eps, int C, float* stats, hipStream_t stream) {
+    MVS_REQUIRE(gamma && beta && running_mean && running_var && stats, MVS_ERR_NULL, "bn_frozen_stats: null pointer argument");
+    MVS_REQUIRE(C >= 1, MVS_ERR_SHAPE, "bn_frozen_stats: bad channel count %d", C);
+    MVS_LAUNCH(bn_frozen_stats_kernel, dim3(mvs_cdiv(C, 64)), dim3(64), 0, stream, gamma, beta, running_mean, running_var, eps, C,
+               stats);
+    return mvs_check_launch("bn_frozen_stats");
+}
+
+// dy: grad wrt relu?(raw*scale + shift) (the skip branch receives dy unchanged, handled by the caller).  draw [V][C] = scale * dyh.
+// dgamma == dbeta == NULL: one launch, no reduction (slots may be NULL).  Otherwise slots [nslots][2][C] (fp64): have_sums != 0 --
+// an input-gradient epilogue given these stats has filled them: one launch; have_sums == 0 -- caller-zeroed, filled by the pass,
+// finished by a one-workgroup launch.
+extern "C" int mvs_bn_relu_bwd_frozen(const float* dy, const float* raw, const float* stats, double* slots, int nslots,
+                                      int have_sums, int relu, long long V, int C, float* draw, float* dgamma, float* dbeta,
+                                      hipStream_t stream) {
+    MVS_REQUIRE(dy && raw && stats && draw, MVS_ERR_NULL, "bn_relu_bwd_frozen: null pointer argument");
+    MVS_REQUIRE(bn_c_ok(C), MVS_ERR_UNSUPPORTED, "bn: C must be 4/8/16/32/64, got %d", C);
+    MVS_REQUIRE(V > 0, MVS_ERR_SHAPE, "bn_relu_bwd_frozen: bad shape V=%lld", V);
+    const bool affine = dgamma || dbeta;
+    MVS_REQUIRE(!affine || (slots && bn_slots_ok(nslots)), MVS_ERR_SHAPE, "bn_relu_bwd_frozen: affine gradients need slot rows (slots=%d)", nslots);
+    const size_t n4 = (size_t)V * C / 4;
+    int g = ew_grid(n4);
+    if (!affine) {
+        MVS_LAUNCH((bn_frozen_bwd_kernel<0>), dim3(g), dim3(256), 0, stream, dy, raw, stats, (double*)nullptr, 0, n4, C, relu, draw,
+                   (float*)nullptr, (float*)nullptr);
+    } else if (have_sums) {
+        MVS_LAUNCH((bn_frozen_bwd_kernel<2>), dim3(g), dim3(256), 0, stream, dy, raw, stats, slots, nslots, n4, C, relu, draw, dgamma,
+                   dbeta);
+    } else {
+        if (g > 1024) g = 1024;
+        MVS_LAUNCH((bn_frozen_bwd_kernel<1>), dim3(g), dim3(256), 0, stream, dy, raw, stats, slots, nslots, n4, C, relu, draw,
+                   (float*)nullptr, (float*)nullptr);
+        int rc = mvs_check_launch("bn_relu_bwd_frozen");
+        if (rc) return rc;
+        MVS_LAUNCH(bn_frozen_finish_kernel, dim3(1), dim3(256), 0, stream, (const double*)slots, nslots, C, dgamma, dbeta);
+    }
+    return mvs_check_launch("bn_relu_bwd_frozen");
+}

@@ -92,18 +92,24 @@ class ConvBnReLU(nn.Module):
         """groups > 1: x holds `groups` equal batch chunks that the reference would pass through this block one
         after the other (the views of a sample); BatchNorm statistics / running-stat updates stay per chunk.
         packed_ws: this block's forward weight image, already written (ops.pack_conv2d_weights; FeatureNet packs all its blocks
-        in one launch)."""
-        if (self.fold_eval and not self.training and not torch.is_grad_enabled() and self.bn.track_running_stats
+        in one launch).
+
+        BatchNorm's mode is the BatchNorm MODULE's (``self.bn.training``), as in the reference's nn.Sequential of stock modules: a
+        block whose BatchNorm is in .eval() -- model.train() with every BatchNorm frozen, or model.eval() with autograd on --
+        normalises with the running statistics, leaves them and num_batches_tracked alone, and is differentiable
+        (ops.BnReLUFn(training=False)); its convolution takes a path without the statistics epilogue."""
+        bn_trains = self.bn.training
+        if (self.fold_eval and not bn_trains and not torch.is_grad_enabled() and self.bn.track_running_stats
                 and self.bn.running_mean is not None and self.bn.affine and hip_conv2d_serves(self.conv, x)):
             w, b = self._folded()
             return ops.conv2d_forward(x, w, b, self.conv.stride[0], negative_slope=0.0)
         if self.hip_conv:
             y = conv2d_maybe_hip(self.conv, x)
-        elif ((ops._ASYNC_WGRAD and self.split_bwd or self.hip_fwd_train) and x.is_cuda and self.training and torch.is_grad_enabled()
-              and self.conv.bias is None and self.conv.groups == 1 and self.conv.dilation == (1, 1)):
+        elif ((ops._ASYNC_WGRAD and self.split_bwd or self.hip_fwd_train) and x.is_cuda and (self.training or not bn_trains)
+              and torch.is_grad_enabled() and self.conv.bias is None and self.conv.groups == 1 and self.conv.dilation == (1, 1)):
             # opt-in side-stream weight gradients (ops.set_async_wgrad): the library convolution with its backward issued as two calls
             hip_fwd = (self.hip_fwd_train and hip_conv2d_serves(self.conv, x) and x.is_contiguous(memory_format=torch.channels_last))
-            if hip_fwd and self.hip_bn and self.conv.out_channels in (4, 8, 16, 32, 64) and self.bn.momentum is not None:
+            if bn_trains and hip_fwd and self.hip_bn and self.conv.out_channels in (4, 8, 16, 32, 64) and self.bn.momentum is not None:
                 # convolution + BatchNorm statistics in one launch, then finalize + apply: no statistics pass over the activation
                 y, slots = ops.Conv2dSplitBwdFn.apply(x, self.conv.weight, self.conv.stride, self.conv.padding, True, True, groups,
                                                       self.split_bwd, packed_ws, self._hip_dgrad(), self.hip_wgrad)
@@ -111,7 +117,11 @@ class ConvBnReLU(nn.Module):
                     count_batch(self.bn, self.training)
                 return ops.BnReLUFn.apply(y, self.bn.weight, self.bn.bias, self.bn.running_mean, self.bn.running_var, True,
                                           self.bn.eps, self.bn.momentum, groups, slots)
-            y = ops.Conv2dSplitBwdFn.apply(x, self.conv.weight, self.conv.stride, self.conv.padding, hip_fwd, False, 1, self.split_bwd)
+            # a frozen block (no statistics epilogue): forward, input gradient and weight gradient all through csrc/conv2d.hip, like
+            # the one-node extractor's -- measured at BASELINE config 2, the library's backward calls made the frozen step 377 ms
+            hip_bwd = hip_fwd and not bn_trains
+            y = ops.Conv2dSplitBwdFn.apply(x, self.conv.weight, self.conv.stride, self.conv.padding, hip_fwd, False, 1, self.split_bwd,
+                                           None, hip_bwd, hip_bwd)
         else:
             y = self.conv(x)
         bn = self.bn
@@ -119,11 +129,12 @@ class ConvBnReLU(nn.Module):
         # channels in a user's own ConvBnReLU, or momentum=None = cumulative average) takes the stock modules
         if (self.hip_bn and y.is_cuda and y.dtype == torch.float32 and y.shape[1] in (4, 8, 16, 32, 64) and bn.momentum is not None
                 and y.is_contiguous(memory_format=torch.channels_last)):
-            for _ in range(groups):
-                count_batch(bn, self.training)
-            momentum = bn.momentum
-            return ops.BnReLUFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, self.training, bn.eps,
-                                      momentum, groups)
+            frozen = not bn_trains and bn.track_running_stats and bn.running_mean is not None
+            if bn_trains or frozen:
+                for _ in range(groups):
+                    count_batch(bn, bn_trains)
+                return ops.BnReLUFn.apply(y, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn_trains, bn.eps,
+                                          bn.momentum, groups)
         if groups > 1:
             return torch.cat([F.relu(bn(c)) for c in y.chunk(groups, 0)], 0)
         return F.relu(bn(y), inplace=True)

@@ -82,6 +82,13 @@ class CostRegNet(nn.Module):
         ws = [getattr(self, name).conv.weight for name, *_ in _REG_ENCODER] + [getattr(self, name)[0].weight for name, *_ in _REG_DECODER]
         return ws + [self.prob.weight]
 
+    def _one_node(self) -> bool:
+        """The one-node regulariser serves two cases: every BatchNorm module trains (batch statistics), or every one is frozen (.eval()
+        on the BatchNorm modules of a net in train mode: fine-tuning with the checkpoint's statistics) and autograd is on.  A mix of
+        the two takes the per-layer graph, where each block follows its own BatchNorm module."""
+        mode = ops.unet_bn_mode(m for m in self.modules() if isinstance(m, nn.BatchNorm3d))
+        return mode == "train" or (mode == "frozen" and torch.is_grad_enabled())
+
     def forward(self, x, tail=None):
         """tail: ops.tail_join_views(self.conv_weights()) made at the START of the model's forward pass (MVSNet._forward): the join of
         the side-stream weight gradients then happens at the end of the backward pass, safely (ops.DeferredJoinFn)."""
@@ -91,7 +98,7 @@ class CostRegNet(nn.Module):
             raise RuntimeError("CostRegNet: bf16 activations are the eval-mode inference path")
         if any(s % 8 for s in x.shape[2:]):
             raise ValueError("CostRegNet needs D,H,W divisible by 8, got %s" % (tuple(x.shape[2:]),))
-        if self.training and x.dtype == torch.float32 and ops.FUSED_REGULARISER:
+        if self.training and x.dtype == torch.float32 and ops.FUSED_REGULARISER and self._one_node():
             # the whole U-Net as one autograd node (ops.UNetRegulariserFn): same kernels, skip gradients summed in the dgrad
             # epilogues, weight gradients on a side stream
             order = [name for name, *_ in _REG_ENCODER] + [name for name, *_ in _REG_DECODER]
@@ -130,6 +137,13 @@ class RefineNet(nn.Module):
 
 
 class MVSNet(nn.Module):
+    """mvsnet.py:95-161.  Modes: ``.train()`` (batch statistics), ``.eval()`` under ``torch.no_grad()`` (inference, BatchNorm folded
+    into the convolutions), and frozen-statistics fine-tuning -- ``.train()`` followed by ``.eval()`` on every BatchNorm module, the
+    only form the reference supports -- where every block normalises with its running statistics, leaves them and
+    num_batches_tracked alone, and all parameters and the images receive gradients.  ``.eval()`` with autograd ON computes that same
+    step: the reference cannot (its eval forward builds the volume in place, mvsnet.py:130-133, which autograd rejects); this
+    forward has no in-place branch."""
+
     def __init__(self, refine=True, align_corners=ALIGN_CORNERS, channels_last_features=True):
         super().__init__()
         self.refine = refine

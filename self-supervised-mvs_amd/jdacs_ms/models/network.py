@@ -62,12 +62,19 @@ class CostRegNet(nn.Module):
         self.conv6 = DeconvBnReLU3D(32, 16, stride=2)
         self.prob0 = ProbConv3d(16)
 
+    def _one_node(self) -> bool:
+        """The one-node regulariser serves two cases: every BatchNorm module trains (batch statistics), or every one is frozen (.eval()
+        on the BatchNorm modules of a net in train mode: fine-tuning with the checkpoint's statistics) and autograd is on.  A mix of
+        the two takes the per-layer graph, where each block follows its own BatchNorm module."""
+        mode = ops.unet_bn_mode(m for m in self.modules() if isinstance(m, nn.BatchNorm3d))
+        return mode == "train" or (mode == "frozen" and torch.is_grad_enabled())
+
     def forward(self, x):
         if x.dim() != 5 or x.shape[1] != 16:
             raise ValueError("CVP CostRegNet expects [B,16,D,H,W], got %s" % (tuple(x.shape),))
         if any(s % 2 for s in x.shape[2:]):
             raise ValueError("CVP CostRegNet needs even D,H,W, got %s" % (tuple(x.shape[2:]),))
-        if self.training and x.dtype == torch.float32 and ops.FUSED_REGULARISER:
+        if self.training and x.dtype == torch.float32 and ops.FUSED_REGULARISER and self._one_node():
             names = [name for name, *_ in _CVP_ENCODER]
             blocks = []
             for i, (name, _, _, stride) in enumerate(_CVP_ENCODER):
@@ -86,6 +93,9 @@ class CostRegNet(nn.Module):
 
 
 class CVPMVSNet(nn.Module):
+    """network.py:77-145.  Besides ``.train()`` and no_grad inference: frozen-statistics fine-tuning (``.train()``, then ``.eval()`` on
+    every BatchNorm module) normalises with the running statistics, does not write them, and trains through every layer; ``.eval()``
+    with autograd on computes the same step (the reference's eval forward works in place and autograd rejects it; this one does not)."""
     batch_views = os.environ.get("MVS_CVP_BATCH_VIEWS", "1") != "0"   # feature pyramid of all views in one batch
 
     def __init__(self, args, align_corners=ALIGN_CORNERS):

@@ -58,6 +58,18 @@ def _bn_step(bn: nn.BatchNorm3d, training: bool):
     return bn.momentum
 
 
+def _bn_trains(bn) -> bool:
+    """Batch statistics (and the running-statistics update) or frozen running statistics: the BatchNorm MODULE's own flag decides,
+    as in nn.BatchNorm*.forward -- ``model.train()`` followed by ``bn.eval()`` on every BatchNorm is the usual way to fine-tune with
+    frozen statistics.  For a whole-model .train() / .eval() the block's flag and its BatchNorm's coincide."""
+    return bool(bn.training)
+
+
+def bn_frozen(bn) -> bool:
+    """frozen statistics: the module is in eval mode and has running statistics to normalise with"""
+    return (not bn.training) and bn.track_running_stats and bn.running_mean is not None
+
+
 class ConvBnReLU3D(nn.Module):
     """jdacs/models/module.py:35-42 (and jdacs-ms/models/modules.py:285-292).  ``skip`` (optional) is
     added after the ReLU, which is how the U-Nets use it (mvsnet.py:70-72)."""
@@ -76,9 +88,10 @@ class ConvBnReLU3D(nn.Module):
             _require_eval(self, "ConvBnReLU3D")
             return ops.conv_bn_relu3d_eval_bf16(x, self.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, skip,
                                                 self.stride, False, bn.eps)
-        momentum = _bn_step(bn, self.training)
+        training = _bn_trains(bn)
+        momentum = _bn_step(bn, training)
         return ops.ConvBnReLU3dFn.apply(x, self.conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                        skip, self.stride, False, self.training, bn.eps, momentum)
+                                        skip, self.stride, False, training, bn.eps, momentum)
 
 
 class DeconvBnReLU3D(nn.Sequential):
@@ -101,9 +114,10 @@ class DeconvBnReLU3D(nn.Sequential):
             _require_eval(self, "DeconvBnReLU3D")
             return ops.conv_bn_relu3d_eval_bf16(x, self[0].weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, skip,
                                                 self.stride, True, bn.eps)
-        momentum = _bn_step(bn, self.training)
+        training = _bn_trains(bn)
+        momentum = _bn_step(bn, training)
         return ops.ConvBnReLU3dFn.apply(x, self[0].weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, skip,
-                                        self.stride, True, self.training, bn.eps, momentum)
+                                        self.stride, True, training, bn.eps, momentum)
 
 
 class ProbConv3d(nn.Conv3d):

@@ -742,13 +742,63 @@ def bn_relu_bwd_slots(gy, x, stats, slots, have_stats, relu=True, groups=1):
     return dx, dgb[0], dgb[1]
 
 
+def bn_frozen_stats(gamma, beta, running_mean, running_var, eps):
+    """stats [4, C] (running_mean, invstd, scale, shift) of a BatchNorm with FROZEN statistics (bn.training == False): the layout
+    of the train-mode stats, so bn_relu_bwd_frozen and conv3d_dgrad(bn=...) read it as it is.  Rows 2 / 3 are mvs_bn_eval_affine's
+    scale / shift bit for bit."""
+    lib = _lib_for(gamma)
+    c = gamma.shape[0]
+    stats = torch.empty((4, c), dtype=torch.float32, device=gamma.device)
+    lib.call("mvs_bn_frozen_stats", _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(eps), c, _p(stats), _stream(gamma))
+    return stats
+
+
+def bn_relu_fwd_frozen(x, stats, skip=None, relu=True):
+    """y = relu?(x*scale + shift) (+ skip) with the frozen stats [4, C] of bn_frozen_stats; x channels-last [B,C,...]."""
+    lib = _lib_for(x)
+    fmt = CL2 if x.dim() == 4 else CL3
+    x = x.contiguous(memory_format=fmt)
+    if skip is not None:
+        skip = skip.contiguous(memory_format=fmt)
+    c = x.shape[1]
+    y = torch.empty_like(x, memory_format=fmt)
+    lib.call("mvs_bn_relu_fwd", _p(x), _p(stats[2]), _p(stats[3]), _p(skip), int(relu), x.numel() // c, c, _p(y), _stream(x))
+    return y
+
+
+def bn_relu_bwd_frozen(gy, x, stats, slots=None, have_sums=False, relu=True, want_affine=True):
+    """Frozen-statistics BatchNorm(+ReLU) backward: (dx, dgamma, dbeta) with dx = scale * gy * [relu active]; one pass over (gy, x).
+    want_affine=False: no reduction at all, (dx, None, None).  Otherwise slots [nslots, 2, C] fp64: have_sums -- they already hold
+    (sum dyh, sum dyh*xhat), written by conv3d_dgrad(bn=(raw, frozen stats, slots)); else zeroed rows (allocated here if None) that
+    the pass fills and a one-workgroup launch finishes.  Never touches the running statistics."""
+    lib = _lib_for(x)
+    fmt = CL2 if x.dim() == 4 else CL3
+    x, gy = x.contiguous(memory_format=fmt), gy.contiguous(memory_format=fmt)
+    c = x.shape[1]
+    dx = torch.empty_like(x, memory_format=fmt)
+    if not want_affine:
+        lib.call("mvs_bn_relu_bwd_frozen", _p(gy), _p(x), _p(stats), None, 0, 0, int(relu), x.numel() // c, c, _p(dx), None, None,
+                 _stream(x))
+        return dx, None, None
+    if slots is None:
+        if have_sums:
+            raise ValueError("bn_relu_bwd_frozen: have_sums needs the slots that hold them")
+        (slots,) = stat_slots(x, 1, bn_nslots(lib, c), c, 1)
+    dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    lib.call("mvs_bn_relu_bwd_frozen", _p(gy), _p(x), _p(stats), _p(slots), slots.shape[-3], int(have_sums), int(relu),
+             x.numel() // c, c, _p(dx), _p(dgb[0]), _p(dgb[1]), _stream(x))
+    return dx, dgb[0], dgb[1]
+
+
 class ConvBnReLU3dFn(torch.autograd.Function):
     """conv3d | conv_transpose3d (bias-free, k3 p1) -> BatchNorm3d -> ReLU (-> + skip, after the ReLU).
 
     Train: batch statistics (slots filled by the conv epilogue, finished in the apply kernel's prologue), running stats
     updated in place.
-    Eval : BatchNorm folded into the conv epilogue (no gradient support -- the reference only
-    evaluates under no_grad, jdacs/eval.py:143)."""
+    Eval / frozen statistics (``training`` False = the BatchNorm module's flag): under no_grad, or when nothing requires a
+    gradient, BatchNorm is folded into the conv epilogue (jdacs/eval.py:143); with a gradient the raw convolution output is kept,
+    the same scale / shift are applied by the BatchNorm apply kernel and the backward is bn_relu_bwd_frozen -> input / weight
+    gradient.  The running statistics are not written."""
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, running_mean, running_var, skip, stride, transposed, training, eps,
@@ -758,13 +808,23 @@ class ConvBnReLU3dFn(torch.autograd.Function):
         x = as_cl3(x)
         cout = weight.shape[1] if transposed else weight.shape[0]
         dev = x.device
-        if not training:
+        ctx.eval_mode = not training
+        if not training and not any(ctx.needs_input_grad):
             scale = torch.empty(cout, dtype=torch.float32, device=dev)
             shift = torch.empty_like(scale)
             lib.call("mvs_bn_eval_affine", _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(eps), cout,
                      _p(scale), _p(shift), st)
             y, _ = conv3d_forward(x, weight, stride, transposed, scale=scale, shift=shift, skip=skip, relu=True)
-            ctx.eval_mode = True
+            return y
+        if not training:
+            # frozen statistics with a gradient: raw convolution output, then the apply pass with the frozen scale / shift
+            if ctx.needs_input_grad[1]:
+                _note_weight_use(weight)
+            stats = bn_frozen_stats(gamma, beta, running_mean, running_var, eps)
+            raw, _ = conv3d_forward(x, weight, stride, transposed)
+            y = bn_relu_fwd_frozen(raw, stats, None if skip is None else as_cl3(skip))
+            ctx.save_for_backward(x, weight, raw, stats)
+            ctx.cfg = (stride, transposed, skip is not None, cout)
             return y
         if ctx.needs_input_grad[1]:
             _note_weight_use(weight)
@@ -781,8 +841,13 @@ class ConvBnReLU3dFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         if ctx.eval_mode:
-            raise NotImplementedError("mvs_amd: backward through eval-mode (folded) BatchNorm is not supported; "
-                                      "call .train() for training or use torch.no_grad() for inference")
+            x, weight, raw, stats = ctx.saved_tensors
+            stride, transposed, has_skip, cout = ctx.cfg
+            gy = as_cl3(gy)
+            draw, dgamma, dbeta = bn_relu_bwd_frozen(gy, raw, stats, want_affine=ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+            gx = conv3d_dgrad(draw, weight, tuple(x.shape), stride, transposed) if ctx.needs_input_grad[0] else None
+            gw = _wgrad_maybe_async(x, draw, weight, stride, transposed) if ctx.needs_input_grad[1] else None
+            return gx, gw, dgamma, dbeta, None, None, (gy if has_skip else None), None, None, None, None, None
         x, weight, raw, stats, slots_b = ctx.saved_tensors
         stride, transposed, has_skip, cout = ctx.cfg
         gy = as_cl3(gy)
@@ -945,11 +1010,20 @@ def _ptrs(base, offs, itemsize=4):
 class UNetRegulariserFn(torch.autograd.Function):
     """x [B,C,D,H,W] -> logits [B,1,D,H,W].  ``prog``: tuple of (transposed, stride, src, skip, eps, momentum) per Conv/Deconv+BN+ReLU
     block (src / skip = index of the block whose output is this block's input / is added after the ReLU; -1 = the volume x / no skip).
-    ``params``: per block weight, gamma, beta, running_mean, running_var; then the prob layer's weight and bias.  Train mode only."""
+    ``params``: per block weight, gamma, beta, running_mean, running_var; then the prob layer's weight and bias.  Every BatchNorm
+    trains (batch statistics); UNetRegulariserFrozenFn is the same node with every BatchNorm frozen."""
 
     @staticmethod
     def forward(ctx, x, prog, *params):
+        return UNetRegulariserFn._run_forward(ctx, False, x, prog, *params)
+
+    @staticmethod
+    def _run_forward(ctx, frozen, x, prog, *params):
+        """frozen: every BatchNorm normalises with its running statistics (bn.training == False) and leaves them alone -- the
+        Python-composed path only: convolution without statistic slots, then the apply pass with the frozen scale / shift; the
+        backward hands the frozen stats to the input-gradient epilogues, so dgamma / dbeta sums still arrive for free."""
         lib = _lib_for(x)
+        ctx.frozen = frozen
         x = as_cl3(x)
         n = len(prog)
         need = ctx.needs_input_grad          # [x, prog, *params]
@@ -977,7 +1051,8 @@ class UNetRegulariserFn(torch.autograd.Function):
             dg_index[n] = len(items)
             items.append((OP_CONV_DGRAD, wp, pshape))
         packed = pack_conv3d_weights(items, x)
-        plan = _unet_plan(lib, prog, tuple(x.shape), tuple(tuple(params[5 * i].shape) for i in range(n)), wp.shape[0]) if C_ENTRY else None
+        plan = (_unet_plan(lib, prog, tuple(x.shape), tuple(tuple(params[5 * i].shape) for i in range(n)), wp.shape[0])
+                if C_ENTRY and not frozen else None)        # (mvs_unet_fwd / mvs_unet_bwd are train-mode passes)
         if plan is not None and plan.ok and _c_entry_allowed(lib, plan, prog, wp):
             dev = x.device
             arena = torch.empty(plan.fwd_floats, dtype=torch.float32, device=dev)
@@ -1002,12 +1077,19 @@ class UNetRegulariserFn(torch.autograd.Function):
             w, gamma, beta, rmean, rvar = params[5 * i:5 * i + 5]
             xin = x if src < 0 else ys[src]
             cout = shapes[i][5]
-            sf, sb = stat_slots(x, 1, bn_nslots(lib, cout), cout, 2)
-            raw, _ = conv3d_forward(xin, w, stride, transposed, slots=sf, packed_ws=packed[i])
-            y, stats = bn_relu_fwd_slots(raw, sf, gamma, beta, rmean, rvar, eps, momentum, ys[skip] if skip >= 0 else None)
+            if frozen:
+                (sb,) = stat_slots(x, 1, bn_nslots(lib, cout), cout, 1)
+                stats = bn_frozen_stats(gamma, beta, rmean, rvar, eps)
+                raw, _ = conv3d_forward(xin, w, stride, transposed, packed_ws=packed[i])
+                y = bn_relu_fwd_frozen(raw, stats, ys[skip] if skip >= 0 else None)
+            else:
+                sf, sb = stat_slots(x, 1, bn_nslots(lib, cout), cout, 2)
+                raw, _ = conv3d_forward(xin, w, stride, transposed, slots=sf, packed_ws=packed[i])
+                y, stats = bn_relu_fwd_slots(raw, sf, gamma, beta, rmean, rvar, eps, momentum, ys[skip] if skip >= 0 else None)
+                stats = stats[0]
             ys.append(y)
             raws.append(raw)
-            statss.append(stats[0])
+            statss.append(stats)
             slots_b.append(sb)
         logits, _ = conv3d_forward(ys[-1], wp, 1, False, shift=bp.contiguous())
         ctx.prog = prog
@@ -1125,8 +1207,13 @@ class UNetRegulariserFn(torch.autograd.Function):
                 if j >= 0:
                     last[j] = min(last[j], i)
 
+        frozen = ctx.frozen
+        affine = [need[2 + 5 * j + 1] or need[2 + 5 * j + 2] for j in range(n)]     # frozen: no sums for a block whose gamma / beta want none
+
         def bn_of(j, i):
             """BatchNorm operands for the input-gradient kernel of consumer i writing block j's gradient, if it completes it"""
+            if frozen and not affine[j]:
+                return None
             return (raws[j], statss[j], slots_b[j]) if (last[j] == i and (i == n or prog[i][2] == j)) else None
 
         grads = [None] * (5 * n + 2)
@@ -1147,7 +1234,10 @@ class UNetRegulariserFn(torch.autograd.Function):
             gy = g[i]
             g[i] = None
             raw, w = raws[i], ws_[i]
-            draw, grads[5 * i + 1], grads[5 * i + 2] = bn_relu_bwd_slots(gy, raw, statss[i], slots_b[i], have[i])
+            if frozen:
+                draw, grads[5 * i + 1], grads[5 * i + 2] = bn_relu_bwd_frozen(gy, raw, statss[i], slots_b[i], have[i], want_affine=affine[i])
+            else:
+                draw, grads[5 * i + 1], grads[5 * i + 2] = bn_relu_bwd_slots(gy, raw, statss[i], slots_b[i], have[i])
             if skip >= 0:                                # y = relu(bn(raw)) + y_skip: the skip source receives gy as it is
                 g[skip] = gy if g[skip] is None else g[skip] + gy
             xin = x if src < 0 else ys[src]
@@ -1179,20 +1269,48 @@ class UNetRegulariserFn(torch.autograd.Function):
         return (gx, None) + tuple(grads)
 
 
+class UNetRegulariserFrozenFn(torch.autograd.Function):
+    """UNetRegulariserFn with every BatchNorm FROZEN (bn.training == False: running statistics, not written; fine-tuning a
+    checkpoint under model.train() + bn.eval()).  Python-composed path only -- the C entry is a train-mode pass."""
+
+    @staticmethod
+    def forward(ctx, x, prog, *params):
+        return UNetRegulariserFn._run_forward(ctx, True, x, prog, *params)
+
+    @staticmethod
+    def backward(ctx, glogits):
+        return UNetRegulariserFn.backward(ctx, glogits)
+
+
+def unet_bn_mode(bns) -> str:
+    """"train": every BatchNorm module takes batch statistics; "frozen": every one normalises with its running statistics;
+    "mixed": anything else (the per-layer graph serves it, each block following its own BatchNorm)."""
+    bns = list(bns)
+    if all(bn.training for bn in bns):
+        return "train"
+    if all((not bn.training) and bn.track_running_stats and bn.running_mean is not None for bn in bns):
+        return "frozen"
+    return "mixed"
+
+
 def unet_regulariser(x, blocks, prob, tail=None):
     """blocks: list of (module-with-.conv/.bn or Sequential(deconv, bn), transposed, stride, src, skip); prob: the bias-only conv.
-    Train-mode fp32 forward of a whole regulariser through UNetRegulariserFn (the modules are parameter containers).
+    fp32 forward of a whole regulariser through UNetRegulariserFn -- every BatchNorm in train mode -- or UNetRegulariserFrozenFn --
+    every BatchNorm frozen (unet_bn_mode) -- (the modules are parameter containers).
     tail: {id(weight): view} of tail_join_views() -- the convolution weights as outputs of the tail node (the node then leaves the join
     of its side-stream weight gradients to it)."""
     from . import nn3d
     tail = tail or {}
     prog, params = [], []
+    mode = unet_bn_mode(b[1] for b in blocks)
+    if mode == "mixed":
+        raise ValueError("mvs_amd: the one-node regulariser needs all its BatchNorm modules in the same mode")
     for conv, bn, transposed, stride, src, skip in blocks:
-        momentum = nn3d._bn_step(bn, True)
+        momentum = nn3d._bn_step(bn, True) if mode == "train" else 0.0      # (frozen: no counter, no running-statistics update)
         prog.append((bool(transposed), int(stride), int(src), int(skip), float(bn.eps), float(momentum)))
         params += [tail.get(id(conv.weight), conv.weight), bn.weight, bn.bias, bn.running_mean, bn.running_var]
     params += [tail.get(id(prob.weight), prob.weight), prob.bias]
-    return UNetRegulariserFn.apply(x, tuple(prog), *params)
+    return (UNetRegulariserFn if mode == "train" else UNetRegulariserFrozenFn).apply(x, tuple(prog), *params)
 
 
 class Conv2dSplitBwdFn(torch.autograd.Function):
@@ -1693,6 +1811,11 @@ class BnReLUFn(torch.autograd.Function):
         vg = x.numel() // c // groups
         ctx.cfg = (training, c, fmt, groups)
         if not training:
+            if any(ctx.needs_input_grad):
+                # frozen statistics with a gradient: the same scale / shift (rows 2, 3 of the frozen stats), x and stats kept
+                stats = bn_frozen_stats(gamma, beta, running_mean, running_var, eps)
+                ctx.save_for_backward(x, stats)
+                return bn_relu_fwd_frozen(x, stats)
             scale = torch.empty(c, dtype=torch.float32, device=x.device)
             shift = torch.empty_like(scale)
             lib.call("mvs_bn_eval_affine", _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(eps), c, _p(scale), _p(shift), st)
@@ -1717,7 +1840,10 @@ class BnReLUFn(torch.autograd.Function):
     def backward(ctx, gy):
         training, c, fmt, groups = ctx.cfg
         if not training:
-            raise NotImplementedError("mvs_amd: backward through eval-mode BatchNorm is not supported")
+            x, stats = ctx.saved_tensors
+            dx, dgamma, dbeta = bn_relu_bwd_frozen(gy.contiguous(memory_format=fmt), x, stats,
+                                                   want_affine=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+            return dx, dgamma, dbeta, None, None, None, None, None, None, None
         x, stats, slots_b = ctx.saved_tensors
         gy = gy.contiguous(memory_format=fmt)
         if ctx.slots_used:
