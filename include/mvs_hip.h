@@ -397,7 +397,15 @@ int mvs_depth_hypo(const float* ref_depths, const double* mats, int B, int H, in
 /* ---- SURVEY.md 8(f)-3, first cut (not used by default): the feature extractors' 2-D convolutions ---------------------
  * nn.Conv2d of jdacs/models/module.py:15-22 as used by FeatureNet (jdacs/models/mvsnet.py:17-34): 3x3 stride 1 pad 1 and
  * 5x5 stride 2 pad 2, 1..32 channels, channels-last images x [N,H,W,Cin], w [Cout][Cin][ks][ks], y [N,Ho,Wo,Cout].
- * op for the workspace query: 0 forward, 1 input gradient, 2 weight gradient. */
+ * op for the workspace query: 0 forward, 1 input gradient, 2 weight gradient; -1 for a shape the op does not serve.
+ * Served: forward and input gradient 1..32 or exactly 64 channels on either side (the stride-2 input gradient: Cin <= 32).
+ * mvs_conv2d_wgrad has an instantiation per input-channel slice width (Cin rounded up to a multiple of 4, 32 for Cin = 64):
+ *   3x3 stride 1: Cin 1..8, 13..16, 29..32, 64     5x5 stride 2: Cin 5..8, 13..16     (Cout 1..32 or 64 in both)
+ * anything else is refused by the query (-1) and by the call (MVS_ERR_UNSUPPORTED) before the first launch.
+ * Launch labels (mvs_launch_trace) name the instantiation: "conv2d_igemm k3|k5 cc4|8|16|32 nb1|2[ stats| stats+xf| stats+bst]",
+ * "conv2d_igemm (pixel pairs) cc4|8[ ...]", "conv2d_dgrad_s2_one_pass|_classes ccN nbN", "conv2d_dgrad_s2" (direct form),
+ * "conv2d_wgrad k3|k5 cxpN nbN" per slice + "conv2d_wgrad_reduce wide|narrow", "conv2d_wgrad_batch[ xf]" +
+ * "conv2d_wgrad_batch_reduce", "conv2d_pack_weights_batch". */
 long long mvs_conv2d_workspace_floats(int op, int N, int H, int W, int Cin, int Cout, int ks, int stride);
 int mvs_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, float* ws, int N, int H, int W, int Cin,
                    int Cout, int ks, int stride, hipStream_t stream);

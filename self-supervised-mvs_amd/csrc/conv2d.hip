@@ -896,10 +896,48 @@ static const int C2_WGRAD_GROUPS = 1024;  // partial images the workspace holds
 static bool c2_shape_ok(int ks, int stride) { return (ks == 3 && stride == 1) || (ks == 5 && stride == 2); }
 static int c2_cc(int ks, int cin) { return ks == 5 ? 8 : (cin <= 4 ? 4 : (cin <= 8 ? 8 : (cin <= 16 ? 16 : 32))); }
 
+// Launch labels (mvs_launch_trace keeps pointers: every label is a literal).  They name the template instantiation that ran, so a
+// test can tell the arms apart: "conv2d_igemm k3 cc16 nb2 stats+xf" = conv2d_igemm_kernel<3, 1, 16, 2, false, STATS, XF>.
+// epilogue index: 0 plain, 1 STATS, 2 STATS + XF, 3 STATS + BST
+#define C2_LAB_EP(p) {p, p " stats", p " stats+xf", p " stats+bst"}
+#define C2_LAB_NB(p) {C2_LAB_EP(p " nb1"), C2_LAB_EP(p " nb2")}
+static const char* const C2_IGEMM_LABEL[4][2][4] = {   // 3x3: [cc 4 / 8 / 16 / 32][NB - 1][epilogue]
+    C2_LAB_NB("conv2d_igemm k3 cc4"), C2_LAB_NB("conv2d_igemm k3 cc8"), C2_LAB_NB("conv2d_igemm k3 cc16"), C2_LAB_NB("conv2d_igemm k3 cc32")};
+static const char* const C2_K5_LABEL[2][3] = {         // 5x5 stride 2 (no input-gradient use, so no BST): [NB - 1][epilogue]
+    {"conv2d_igemm k5 cc8 nb1", "conv2d_igemm k5 cc8 nb1 stats", "conv2d_igemm k5 cc8 nb1 stats+xf"},
+    {"conv2d_igemm k5 cc8 nb2", "conv2d_igemm k5 cc8 nb2 stats", "conv2d_igemm k5 cc8 nb2 stats+xf"}};
+static const char* const C2_PP_LABEL[2][4] = {         // [cc 4 / 8][epilogue]; XF has no cc 4 instantiation (refused before the launch)
+    {"conv2d_igemm (pixel pairs) cc4", "conv2d_igemm (pixel pairs) cc4 stats", nullptr, "conv2d_igemm (pixel pairs) cc4 stats+bst"},
+    C2_LAB_EP("conv2d_igemm (pixel pairs) cc8")};
+#define C2_LAB_CCNB(p) {{p " cc4 nb1", p " cc4 nb2"}, {p " cc8 nb1", p " cc8 nb2"}, {p " cc16 nb1", p " cc16 nb2"}, {p " cc32 nb1", p " cc32 nb2"}}
+static const char* const C2_S2D_LABEL[4][2] = C2_LAB_CCNB("conv2d_dgrad_s2_one_pass");     // [cc][NB - 1]
+static const char* const C2_S2C_LABEL[4][2] = C2_LAB_CCNB("conv2d_dgrad_s2_classes");
+static const char* const C2_WGRAD_LABEL[6][2] = {   // [3x3: CXP 4 / 8 / 16 / 32, 5x5: CXP 8 / 16][NB - 1]
+    {"conv2d_wgrad k3 cxp4 nb1", "conv2d_wgrad k3 cxp4 nb2"}, {"conv2d_wgrad k3 cxp8 nb1", "conv2d_wgrad k3 cxp8 nb2"},
+    {"conv2d_wgrad k3 cxp16 nb1", "conv2d_wgrad k3 cxp16 nb2"}, {"conv2d_wgrad k3 cxp32 nb1", "conv2d_wgrad k3 cxp32 nb2"},
+    {"conv2d_wgrad k5 cxp8 nb1", "conv2d_wgrad k5 cxp8 nb2"}, {"conv2d_wgrad k5 cxp16 nb1", "conv2d_wgrad k5 cxp16 nb2"}};
+#undef C2_LAB_EP
+#undef C2_LAB_NB
+#undef C2_LAB_CCNB
+static int c2_cc_index(int cc) { return cc == 4 ? 0 : (cc == 8 ? 1 : (cc == 16 ? 2 : 3)); }
+static int c2_epilogue_index(const double* slots, const float* in_stats, const float* bn_raw) {
+    return !slots ? 0 : (bn_raw ? 3 : (in_stats ? 2 : 1));
+}
+
+// The per-layer weight gradient (conv2d_wgrad_kernel) is instantiated for input-channel slices that round up to 4 / 8 / 16 / 32
+// channels (3x3) or to 8 / 16 (5x5); a layer's slice is its Cin up to 32 channels and 32 for the 64-channel layers.  Row of
+// C2_WGRAD_LABEL, or -1 where no instantiation exists (3x3: Cin 9..12 and 17..28; 5x5: Cin <= 4, 9..12 and > 16).
+static int c2_wgrad_row(int ks, int Cin) {
+    const int cxp = ((Cin > 32 ? 32 : Cin) + 3) / 4 * 4;
+    if (ks == 3) return cxp == 4 ? 0 : (cxp == 8 ? 1 : (cxp == 16 ? 2 : (cxp == 32 ? 3 : -1)));
+    return cxp == 8 ? 4 : (cxp == 16 ? 5 : -1);
+}
+
 extern "C" long long mvs_conv2d_workspace_floats(int op, int N, int H, int W, int Cin, int Cout, int ks, int stride) {
     if (!c2_shape_ok(ks, stride) || Cin < 1 || Cin > 64 || Cout < 1 || Cout > 64) return -1;
     const int nt = ks * ks;
     if (op == 2) {   // one <= 32 x <= 32 channel slice at a time
+        if ((Cin > 32 && Cin != 64) || (Cout > 32 && Cout != 64) || c2_wgrad_row(ks, Cin) < 0) return -1;   // what mvs_conv2d_wgrad serves
         const int cxs = Cin > 32 ? 32 : (Cin + 3) / 4 * 4, cgs = Cout > 32 ? 32 : (Cout + 15) / 16 * 16;
         // one partial image per persistent workgroup the launch will actually use (knob "wgrad2d_groups", evaluated now: the
         // caller queries the size right before the call), not the 1024-image ceiling (37.7 MB instead of 9.4 MB per 32x32 layer)
@@ -964,6 +1002,7 @@ static int c2_run_igemm(const float* x, const float* w, const float* bias, float
     if (ks == 3 && stride == 1 && Cout <= 8 && (cc == 4 || cc == 8) && g_tune.conv2d_pp) {
         // narrow layers (3 -> 8, 8 -> 8 of FeatureNet): pixel pairs fill the MFMA's 16 columns (knob "conv2d_pp")
         const int totalp = nch * c2_ksteps(12, cc) * 256;
+        MVS_REQUIRE(!(slots && in_stats && !bn_raw) || cc == 8, MVS_ERR_UNSUPPORTED, "conv2d: a normalised input has a multiple of 4 channels, got %d", Cin);
         if (!ws_packed)
             MVS_LAUNCH(conv2d_pack_kernel, dim3(mvs_cdiv(totalp, 256)), dim3(256), 0, st, w, ws, nt, cc, Cin, Cout, 1, transposed, totalp, -1, 1, wcl);
         a.wp = ws;
@@ -972,28 +1011,28 @@ static int c2_run_igemm(const float* x, const float* w, const float* bias, float
             if (cc == 4) MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 4, 1, true, true, false, true>), gridp, dim3(256), 0, st, a);
             else MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 8, 1, true, true, false, true>), gridp, dim3(256), 0, st, a);
         } else if (slots && in_stats) {
-            MVS_REQUIRE(cc == 8, MVS_ERR_UNSUPPORTED, "conv2d: a normalised input has a multiple of 4 channels, got %d", Cin);
             MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 8, 1, true, true, true>), gridp, dim3(256), 0, st, a);
         } else if (slots) {
             if (cc == 4) MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 4, 1, true, true>), gridp, dim3(256), 0, st, a);
             else MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 8, 1, true, true>), gridp, dim3(256), 0, st, a);
         } else if (cc == 4) MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 4, 1, true>), gridp, dim3(256), 0, st, a);
         else MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 8, 1, true>), gridp, dim3(256), 0, st, a);
-        return mvs_check_launch("conv2d_igemm (pixel pairs)");
+        return mvs_check_launch(C2_PP_LABEL[cc == 4 ? 0 : 1][c2_epilogue_index(slots, in_stats, bn_raw)]);
     }
     const int total = nch * c2_ksteps(nt, cc) * a.nb_total * 256;
+    const int nb = a.nb_total <= 2 ? a.nb_total : 2;   // 16-wide Cout tiles per workgroup; the rest over blockIdx.y
+    MVS_REQUIRE(a.nb_total % nb == 0, MVS_ERR_UNSUPPORTED, "conv2d: %d output channels not supported (1..32, 33..64 in steps of 32)", Cout);
     if (!ws_packed)
         MVS_LAUNCH(conv2d_pack_kernel, dim3(mvs_cdiv(total, 256)), dim3(256), 0, st, w, ws, nt, cc, Cin, Cout, a.nb_total, transposed, total, -1, 0, wcl);
     a.wp = ws;
-    const int nb = a.nb_total <= 2 ? a.nb_total : 2;   // 16-wide Cout tiles per workgroup; the rest over blockIdx.y
     dim3 grid(N * a.nth * a.ntw, mvs_cdiv(a.nb_total, nb));
-    MVS_REQUIRE(a.nb_total % nb == 0, MVS_ERR_UNSUPPORTED, "conv2d: %d output channels not supported (1..32, 33..64 in steps of 32)", Cout);
     if (ks == 5) c2_launch<5, 2, 8>(a, nb, grid, st);
     else if (cc == 4) c2_launch<3, 1, 4>(a, nb, grid, st);
     else if (cc == 8) c2_launch<3, 1, 8>(a, nb, grid, st);
     else if (cc == 16) c2_launch<3, 1, 16>(a, nb, grid, st);
     else c2_launch<3, 1, 32>(a, nb, grid, st);
-    return mvs_check_launch("conv2d_igemm");
+    const int ep = c2_epilogue_index(slots, in_stats, bn_raw);
+    return mvs_check_launch(ks == 5 ? C2_K5_LABEL[nb - 1][ep < 3 ? ep : 1] : C2_IGEMM_LABEL[c2_cc_index(cc)][nb - 1][ep]);
 }
 
 static int c2_check(const char* what, int N, int H, int W, int Cin, int Cout, int ks, int stride) {
@@ -1139,13 +1178,14 @@ extern "C" int mvs_conv2d_dgrad_wl(const float* gy, const float* w, float* gx, f
     else MVS_LAUNCH((conv2d_igemm_kernel<3, 1, CCV, 2, false, false, false, false, true>), grid, dim3(256), 0, stream, a);
         if (cc == 8) { MVS_S2D_CASE(8) } else if (cc == 16) { MVS_S2D_CASE(16) } else if (cc == 32) { MVS_S2D_CASE(32) } else { MVS_S2D_CASE(4) }
 #undef MVS_S2D_CASE
-        return mvs_check_launch("conv2d_dgrad_s2_one_pass");
+        return mvs_check_launch(C2_S2D_LABEL[c2_cc_index(cc)][nbt - 1]);
     }
     if (g_tune.conv2d_s2_mfma) {
         // four parity classes, each a 3x3 stride-1 pass over gy on the coarse grid with its own (partly empty) weight image
         const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
         const int cc = c2_cc(3, Cout), nch = mvs_cdiv(Cout, cc), nbt = mvs_cdiv(Cin, 16);
         const int total_w = nch * c2_ksteps(9, cc) * nbt * 256;
+        MVS_REQUIRE(nbt <= 2, MVS_ERR_UNSUPPORTED, "conv2d_dgrad: the 5x5 stride-2 layers have <= 32 input channels");
         for (int cls = 0; cls < 4; ++cls) {
             Conv2dArgs a = {};
             a.x = gy; a.bias = nullptr; a.y = gx; a.N = N; a.Hi = Ho; a.Wi = Wo; a.Cin = Cout; a.Cout = Cin;
@@ -1156,14 +1196,13 @@ extern "C" int mvs_conv2d_dgrad_wl(const float* gy, const float* w, float* gx, f
             float* wpc = ws + (size_t)cls * total_w;
             MVS_LAUNCH(conv2d_pack_kernel, dim3(mvs_cdiv(total_w, 256)), dim3(256), 0, stream, w, wpc, 9, cc, Cout, Cin, nbt, 0, total_w, cls, 0, w_channels_last);
             a.wp = wpc;
-            MVS_REQUIRE(nbt <= 2, MVS_ERR_UNSUPPORTED, "conv2d_dgrad: the 5x5 stride-2 layers have <= 32 input channels");
             dim3 grid(N * a.nth * a.ntw, 1);
             if (cc == 8) c2_launch<3, 1, 8>(a, nbt, grid, stream);
             else if (cc == 16) c2_launch<3, 1, 16>(a, nbt, grid, stream);
             else if (cc == 32) c2_launch<3, 1, 32>(a, nbt, grid, stream);
             else c2_launch<3, 1, 4>(a, nbt, grid, stream);
         }
-        return mvs_check_launch("conv2d_dgrad_s2_classes");
+        return mvs_check_launch(C2_S2C_LABEL[c2_cc_index(cc)][nbt - 1]);
     }
     MVS_REQUIRE(!w_channels_last, MVS_ERR_UNSUPPORTED, "conv2d_dgrad: the direct stride-2 form (knob conv2d_s2_mfma = 0) reads a contiguous weight");
     const size_t total = (size_t)N * H * W * Cin;
@@ -1187,6 +1226,14 @@ extern "C" int mvs_conv2d_wgrad(const float* x, const float* gy, float* gw, floa
     const int Ho = stride == 1 ? H : (H - 1) / 2 + 1, Wo = stride == 1 ? W : (W - 1) / 2 + 1;
     const int gmax = g_tune.wgrad2d_groups < 1 ? 1 : (g_tune.wgrad2d_groups > C2_WGRAD_GROUPS ? C2_WGRAD_GROUPS : g_tune.wgrad2d_groups);
     const int nt = ks * ks;
+    // every slice of a layer has the same width (Cin <= 32: one; Cin == 64: two of 32), so one look at the table settles the whole
+    // layer before the first launch
+    const int row = c2_wgrad_row(ks, Cin);
+    MVS_REQUIRE(row >= 0, MVS_ERR_UNSUPPORTED,
+                "conv2d_wgrad: %d input channels not served for the %dx%d layer (3x3: 1..8, 13..16, 29..32, 64; 5x5: 5..8, 13..16)", Cin, ks, ks);
+    const int nth = mvs_cdiv(Ho, 8), ntw = mvs_cdiv(Wo, 32);
+    const int ntiles = N * nth * ntw, groups = ntiles < gmax ? ntiles : gmax;     // partial images: the same for every slice
+    const bool wide = groups > 16;      // which reduce sums them (one decision for the launch and for its label)
     // layers wider than 32 channels (the feature pyramid's 64) run as <= 32 x <= 32 channel slices, one after the other
     for (int ci0 = 0; ci0 < Cin; ci0 += 32)
         for (int co0 = 0; co0 < Cout; co0 += 32) {
@@ -1194,33 +1241,33 @@ extern "C" int mvs_conv2d_wgrad(const float* x, const float* gy, float* gw, floa
             a.x = x; a.g = gy; a.part = ws; a.N = N; a.Hi = H; a.Wi = W; a.Ho = Ho; a.Wo = Wo;
             a.CX = Cin - ci0 < 32 ? Cin - ci0 : 32; a.CG = Cout - co0 < 32 ? Cout - co0 : 32;
             a.xs = Cin; a.x0 = ci0; a.gs = Cout; a.g0 = co0;
-            a.nth = mvs_cdiv(a.Ho, 8); a.ntw = mvs_cdiv(a.Wo, 32);
-            const int ntiles = N * a.nth * a.ntw, groups = ntiles < gmax ? ntiles : gmax;
+            a.nth = nth; a.ntw = ntw;
             const int cxp = (a.CX + 3) / 4 * 4, nb = mvs_cdiv(a.CG, 16);
-            bool ok = true;
-            if (ks == 3) {
-                if (cxp == 4) { if (nb == 1) c2_wgrad_launch<3, 1, 4, 1>(a, groups, stream); else c2_wgrad_launch<3, 1, 4, 2>(a, groups, stream); }
-                else if (cxp == 8) { if (nb == 1) c2_wgrad_launch<3, 1, 8, 1>(a, groups, stream); else c2_wgrad_launch<3, 1, 8, 2>(a, groups, stream); }
-                else if (cxp == 16) { if (nb == 1) c2_wgrad_launch<3, 1, 16, 1>(a, groups, stream); else c2_wgrad_launch<3, 1, 16, 2>(a, groups, stream); }
-                else if (cxp == 32) { if (nb == 1) c2_wgrad_launch<3, 1, 32, 1>(a, groups, stream); else c2_wgrad_launch<3, 1, 32, 2>(a, groups, stream); }
-                else ok = false;
-            } else {
-                if (cxp == 8) { if (nb == 1) c2_wgrad_launch<5, 2, 8, 1>(a, groups, stream); else c2_wgrad_launch<5, 2, 8, 2>(a, groups, stream); }
-                else if (cxp == 16) { if (nb == 1) c2_wgrad_launch<5, 2, 16, 1>(a, groups, stream); else c2_wgrad_launch<5, 2, 16, 2>(a, groups, stream); }
-                else ok = false;
+            switch (row * 2 + nb - 1) {
+                case 0: c2_wgrad_launch<3, 1, 4, 1>(a, groups, stream); break;
+                case 1: c2_wgrad_launch<3, 1, 4, 2>(a, groups, stream); break;
+                case 2: c2_wgrad_launch<3, 1, 8, 1>(a, groups, stream); break;
+                case 3: c2_wgrad_launch<3, 1, 8, 2>(a, groups, stream); break;
+                case 4: c2_wgrad_launch<3, 1, 16, 1>(a, groups, stream); break;
+                case 5: c2_wgrad_launch<3, 1, 16, 2>(a, groups, stream); break;
+                case 6: c2_wgrad_launch<3, 1, 32, 1>(a, groups, stream); break;
+                case 7: c2_wgrad_launch<3, 1, 32, 2>(a, groups, stream); break;
+                case 8: c2_wgrad_launch<5, 2, 8, 1>(a, groups, stream); break;
+                case 9: c2_wgrad_launch<5, 2, 8, 2>(a, groups, stream); break;
+                case 10: c2_wgrad_launch<5, 2, 16, 1>(a, groups, stream); break;
+                default: c2_wgrad_launch<5, 2, 16, 2>(a, groups, stream); break;
             }
-            MVS_REQUIRE(ok, MVS_ERR_UNSUPPORTED, "conv2d_wgrad: input channels %d not supported for the %dx%d layer", Cin, ks, ks);
-            rc = mvs_check_launch("conv2d_wgrad");
+            rc = mvs_check_launch(C2_WGRAD_LABEL[row][nb - 1]);
             if (rc) return rc;
             const int n = a.CG * a.CX * nt;
-            if (groups > 16)
+            if (wide)
                 MVS_LAUNCH(conv2d_wgrad_reduce_wide_kernel, dim3(mvs_cdiv(nt * cxp * nb * 16, 16)), dim3(256), 0, stream, (const float*)ws, groups, nt,
                            a.CX, cxp, a.CG, nb * 16, gw, Cin, ci0, co0);
             else
                 MVS_LAUNCH(conv2d_wgrad_reduce_kernel, dim3(mvs_cdiv(n, 256)), dim3(256), 0, stream, (const float*)ws, groups, nt, a.CX, cxp, a.CG,
                            nb * 16, gw, Cin, ci0, co0);
         }
-    return mvs_check_launch("conv2d_wgrad_reduce");
+    return mvs_check_launch(wide ? "conv2d_wgrad_reduce wide" : "conv2d_wgrad_reduce narrow");
 }
 
 // ---- all layers' weight gradients in one launch -------------------------------------------------------------------------------
@@ -1319,7 +1366,7 @@ static int wg2_run(int n, const float* const* x, const float* const* x_stats, in
         if (wgc[1]) MVS_LAUNCH((conv2d_wgrad_batch_kernel<1>), dim3(wgc[1]), dim3(256), 0, stream, b);
         if (wgc[0]) MVS_LAUNCH((conv2d_wgrad_batch_kernel<0>), dim3(wgc[0]), dim3(256), 0, stream, b);
     }
-    int rc = mvs_check_launch("conv2d_wgrad_batch");
+    int rc = mvs_check_launch(any_xf ? "conv2d_wgrad_batch xf" : "conv2d_wgrad_batch");
     if (rc) return rc;
     const Wg2Layer& last = b.l[n - 1];
     MVS_LAUNCH(conv2d_wgrad_batch_reduce_kernel, dim3(last.rb0 + last.nrb), dim3(256), 0, stream, b);

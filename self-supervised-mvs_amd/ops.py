@@ -2299,8 +2299,9 @@ def depth_hypotheses(ref_depths: torch.Tensor, mats: torch.Tensor) -> torch.Tens
 def _c2_ws(lib, op, n, h, w, cin, cout, ks, stride, like):
     nfl = lib.raw("mvs_conv2d_workspace_floats", op, n, h, w, cin, cout, ks, stride)
     if nfl < 0:
-        raise ValueError("conv2d: unsupported shape (3x3 stride 1 or 5x5 stride 2, 1..32 or 64 channels): Cin=%d Cout=%d k=%d s=%d"
-                         % (cin, cout, ks, stride))
+        raise ValueError("conv2d: unsupported shape (3x3 stride 1 or 5x5 stride 2, 1..32 or 64 channels%s): Cin=%d Cout=%d k=%d s=%d"
+                         % ("; weight gradient: 3x3 with Cin 1..8, 13..16, 29..32, 64, 5x5 with Cin 5..8, 13..16" if op == 2 else "",
+                            cin, cout, ks, stride))
     return torch.empty(nfl, dtype=torch.float32, device=like.device)
 
 
