@@ -496,6 +496,67 @@ int mvs_feature_bwd(int n, const MvsFeatBlock* blocks, int N, int G, const float
                     float* dgrad_ws, float* const* gw, float* wgrad_ws_main, float* wgrad_ws_side, float* const* dgamma,
                     float* const* dbeta, int early_from, hipStream_t main_stream, hipStream_t side_stream, int* side_stream_used);
 
+/* ---- RefineNet (jdacs/models/mvsnet.py:77-92) with no library kernel (csrc/refine_kernels.h, csrc/feature_pass.cpp) -------------
+ * out = depth + relu(bn(conv(... ConvBnReLU x3 (cat(bilinear(img, 1/4), depth)) ...))): img [B,3,H,W] fp32 NCHW whose batch stride
+ * (in floats) is an argument -- MVSNet passes imgs[:, 0] of [B,N,3,H,W] --, depth [B,h,w] contiguous with h = H/4, w = W/4 (floor);
+ * any other depth size is refused (MVS_ERR_SHAPE, both shapes in the message).  Launch labels: "refine_assemble",
+ * "refine_assemble_bwd", "refine_tail", "refine_tail frozen", "refine_tail eval", "refine_tail_bwd_reduce", "refine_tail_bwd".
+ * mvs_refine_assemble: x0 [B,h,w,4] channels-last (16-byte aligned) = (mean of img's pixels (4y+1..4y+2, 4x+1..4x+2) per colour,
+ *   depth): bit-identical to F.interpolate(scale_factor=0.25, mode='bilinear') + cat.  One launch.
+ * mvs_refine_assemble_bwd: gx0 [B,h,w,4], gy [B,h,w] -> gimg [B,3,H,W] contiguous (0.25 * gx0 on those four pixels, zero elsewhere;
+ *   NULL: not computed) and gdepth [B,h,w] = gy + gx0[..., 3].  One launch, no atomics.
+ * mvs_refine_tail_fwd: y = depth + relu(gamma * (raw - mean) * invstd + beta) over raw / depth / y [V] with the batch statistics
+ *   finished in fp64 from slots [nslots][2] (sum, sum of squares: what mvs_conv2d_fwd_stats adds for Cout = 1; nslots a power of two
+ *   <= 256); writes stats [4] = (mean, invstd, scale, shift) and updates running_mean / running_var [1] (both NULL: not tracked)
+ *   with `momentum` and the unbiased variance.
+ * mvs_refine_tail_fwd_frozen: the same with stats [4] = mvs_bn_frozen_stats(..., C = 1, ...); writes y only.
+ * mvs_refine_tail_bwd: gy [V] -> draw [V] (gradient w.r.t. raw), dgamma / dbeta [1] (NULL: not written).  Two launches: per-workgroup
+ *   fp64 records (sum dyh, sum dyh * xhat) into rec (512 doubles of scratch), then the apply pass, which sums them in a fixed order:
+ *   two calls give the same bits.  frozen != 0: draw = scale * dyh.  The gradient towards depth is gy itself.
+ * mvs_refine_tail_eval: y = depth + relu(conv3x3(x, w) + bias), x [B,h,w,32] channels-last, w [1][32][3][3], bias [1] (BatchNorm
+ *   folded in by the caller).  One launch.
+ * mvs_conv2d_relu_fwd_packed: y = relu(conv3x3 stride 1 (x) + bias) with the forward weight image already in `packed`
+ *   (mvs_conv2d_pack_weights_batch): no pack launch.
+ * mvs_refine_fwd / _eval_fwd / _bwd take the image's H, W and the depth map's h, w_ (refused unless h = H/4, w_ = W/4).
+ * mvs_refine_fwd: the whole forward pass in train mode (frozen = 0: batch statistics, running statistics updated) or with frozen
+ *   statistics (frozen != 0: running_* are only read).  w / gamma / beta / running_* / eps / momentum: the four blocks' parameters
+ *   (w[i] contiguous [Cout][Cin][3][3], 4 -> 32 -> 32 -> 32 -> 1).  Caller's buffers: x0 [B,h,w,4]; packed[i]
+ *   (mvs_conv2d_workspace_floats(0, ...) floats); raw[0..2] / y2 [B,h,w,32], raw[3] [B,h,w]; stats[i] [4][Cout]; slots[i]
+ *   [nslots[i]][2][Cout] fp64, zeroed (nslots[3] a power of two <= 256); out [B,h,w].  10 launches (frozen: 12).
+ * mvs_refine_eval_fwd: eval mode without a gradient, 5 launches: packed[3] / bias[3] are the weight images and biases of the three
+ *   32-channel blocks with BatchNorm folded in, wtail / btail the folded 32 -> 1 layer; buf_a / buf_b [B,h,w,32].
+ * mvs_refine_bwd: gout [B,h,w] -> gw[4] (contiguous, every layer), dgamma[i] / dbeta[i], gimg (or NULL), gdepth.  Work space:
+ *   gbuf[0..2], draw[0..2] [B,h,w,32], draw[3] [B,h,w], gx0 [B,h,w,4], slots_b[0..2] (zeroed, like slots), tail_rec (512 doubles),
+ *   dgrad_ws (the largest mvs_conv2d_workspace_floats(1, ...) of the four layers), wgrad_ws (the largest of
+ *   mvs_conv2d_workspace_floats(2, ...) of layers 0 and 3 and mvs_conv2d_wgrad_batch_workspace_floats of layers 1, 2).  One stream. */
+int mvs_refine_assemble(const float* img, long long img_batch_stride, const float* depth, float* x0, int B, int H, int W, int h, int w,
+                        hipStream_t stream);
+int mvs_refine_assemble_bwd(const float* gx0, const float* gy, float* gimg, float* gdepth, int B, int H, int W, int h, int w,
+                            hipStream_t stream);
+int mvs_refine_tail_fwd(const float* raw, const float* depth, const double* slots, int nslots, long long V, const float* gamma,
+                        const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* stats, float* y,
+                        hipStream_t stream);
+int mvs_refine_tail_fwd_frozen(const float* raw, const float* depth, const float* stats, const float* beta, long long V, float* y,
+                               hipStream_t stream);
+int mvs_refine_tail_bwd(const float* gy, const float* raw, const float* stats, const float* beta, int frozen, long long V, double* rec,
+                        float* draw, float* dgamma, float* dbeta, hipStream_t stream);
+int mvs_refine_tail_eval(const float* x, const float* w, const float* bias, const float* depth, float* y, int B, int h, int w_,
+                         hipStream_t stream);
+int mvs_conv2d_relu_fwd_packed(const float* x, float* packed, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                               hipStream_t stream);
+int mvs_refine_fwd(int frozen, int B, int H, int W, int h, int w_, const float* img, long long img_batch_stride, const float* depth,
+                   const float* const* w, const float* const* gamma, const float* const* beta, float* const* running_mean,
+                   float* const* running_var, const float* eps, const float* momentum, float* x0, float* const* packed,
+                   float* const* raw, float* y2, float* const* stats, double* const* slots, const int* nslots, float* out,
+                   hipStream_t stream);
+int mvs_refine_eval_fwd(int B, int H, int W, int h, int w_, const float* img, long long img_batch_stride, const float* depth, float* const* packed,
+                        const float* const* bias, const float* wtail, const float* btail, float* x0, float* buf_a, float* buf_b,
+                        float* out, hipStream_t stream);
+int mvs_refine_bwd(int frozen, int B, int H, int W, int h, int w_, const float* const* w, const float* x0, const float* const* raw, const float* y2,
+                   const float* const* stats, const float* beta3, double* const* slots_b, const int* nslots, double* tail_rec,
+                   const float* gout, float* const* gbuf, float* const* draw, float* gx0, float* dgrad_ws, float* const* gw,
+                   float* wgrad_ws, float* const* dgamma, float* const* dbeta, float* gimg, float* gdepth, hipStream_t stream);
+
 /* ---- Wide forward 2-D convolutions: the frozen VGG-style trunk in front of the NMF (csrc/conv2d_wide_kernels.h) -----------------
  * 3x3, stride 1, pad 1, fp32, forward only, channels-last images x [N,H,W,Cin] -> y [N,H,W,Cout]; Cin = 3 or 32..512 and
  * Cout = 32..512 in steps of 32 (the existing mvs_conv2d_* family serves 1..32 or exactly 64 channels).  Implicit GEMM on the

@@ -48,6 +48,18 @@ SIGNATURES = {
                              _i, _f, _f, _s]),
     "mvs_feature_bwd": (_i, [_i, C.POINTER(MvsFeatBlock), _i, _i, _f, _pp, _f, _i, _i, _pp, _f, _pp, _pp, C.POINTER(_i), _f, _pp, _pp, _f, _f,
                              _pp, _f, _f, _pp, _pp, _i, _s, _s, C.POINTER(_i)]),
+    "mvs_refine_assemble": (_i, [_f, _ll, _f, _f, _i, _i, _i, _i, _i, _s]),
+    "mvs_refine_assemble_bwd": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _s]),
+    "mvs_refine_tail_fwd": (_i, [_f, _f, _f, _i, _ll, _f, _f, _fl, _fl, _f, _f, _f, _f, _s]),
+    "mvs_refine_tail_fwd_frozen": (_i, [_f, _f, _f, _f, _ll, _f, _s]),
+    "mvs_refine_tail_bwd": (_i, [_f, _f, _f, _f, _i, _ll, _f, _f, _f, _f, _s]),
+    "mvs_refine_tail_eval": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _s]),
+    "mvs_conv2d_relu_fwd_packed": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _s]),
+    "mvs_refine_fwd": (_i, [_i, _i, _i, _i, _i, _i, _f, _ll, _f, _pp, _pp, _pp, _pp, _pp, C.POINTER(_fl), C.POINTER(_fl), _f, _pp, _pp, _f, _pp, _pp,
+                            C.POINTER(_i), _f, _s]),
+    "mvs_refine_eval_fwd": (_i, [_i, _i, _i, _i, _i, _f, _ll, _f, _pp, _pp, _f, _f, _f, _f, _f, _f, _s]),
+    "mvs_refine_bwd": (_i, [_i, _i, _i, _i, _i, _i, _pp, _f, _pp, _f, _pp, _f, _pp, C.POINTER(_i), _f, _f, _pp, _pp, _f, _f, _pp, _f, _pp, _pp, _f,
+                            _f, _s]),
     "mvs_conv2d_dgrad_wl": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     "mvs_conv2d_fwd_wl": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     "mvs_version": (_i, []),

@@ -1627,3 +1627,6 @@ extern "C" int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const floa
                                   float* buf_a, float* buf_b, float* ws, float* out, int N, int H, int W, hipStream_t stream) {
     return mvs_conv_trunk_fwd_arith(n, layers, (const void* const*)packed, bias, x, buf_a, buf_b, ws, out, N, H, W, MVS_ARITH_F32, stream);
 }
+
+// ---- RefineNet head and tail (refine_kernels.h): input assembly, one-channel BatchNorm + ReLU + residual, folded eval tail ----
+#include "refine_kernels.h"

@@ -200,3 +200,135 @@ extern "C" int mvs_feature_bwd(int n, const MvsFeatBlock* blk, int N, int G, con
                         wgrad_ws_main, main_stream));
     return MVS_OK;          // (the Closer joins side -> main and reports)
 }
+
+// ---- RefineNet (jdacs/models/mvsnet.py:77-92) as one C call per pass ---------------------------------------------------------------
+// image [B,3,H,W] (any batch stride) + depth [B,h,w], h = H/4, w = W/4 -> x0 [B,h,w,4] (refine_kernels.h) -> ConvBnReLU 4 -> 32 -> 32
+// -> 32 -> 1 -> depth + relu(bn(.)).  Blocks 0 and 1 are normalised by their consumers while those stage their input (as in
+// mvs_feature_fwd); block 2's output y2 is materialised for the 32 -> 1 convolution, whose epilogue sums the one-channel statistics
+// the tail finishes.  frozen != 0: every block normalises with its running statistics (mvs_bn_frozen_stats); nothing writes them.
+extern "C" {
+int mvs_conv2d_wgrad(const float* x, const float* gy, float* gw, float* ws, int N, int H, int W, int Cin, int Cout, int ks, int stride,
+                     hipStream_t stream);
+int mvs_conv2d_relu_fwd_packed(const float* x, float* packed, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                               hipStream_t stream);
+int mvs_bn_frozen_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, int C,
+                        float* stats, hipStream_t stream);
+int mvs_bn_relu_fwd(const float* x, const float* scale, const float* shift, const float* skip, int relu, long long V, int C, float* y,
+                    hipStream_t stream);
+int mvs_bn_relu_bwd_frozen(const float* dy, const float* raw, const float* stats, double* slots, int nslots, int have_sums, int relu,
+                           long long V, int C, float* draw, float* dgamma, float* dbeta, hipStream_t stream);
+int mvs_refine_assemble(const float* img, long long img_batch_stride, const float* depth, float* x0, int B, int H, int W, int h, int w,
+                        hipStream_t stream);
+int mvs_refine_assemble_bwd(const float* gx0, const float* gy, float* gimg, float* gdepth, int B, int H, int W, int h, int w,
+                            hipStream_t stream);
+int mvs_refine_tail_fwd(const float* raw, const float* depth, const double* slots, int nslots, long long V, const float* gamma,
+                        const float* beta, float eps, float momentum, float* running_mean, float* running_var, float* stats, float* y,
+                        hipStream_t stream);
+int mvs_refine_tail_fwd_frozen(const float* raw, const float* depth, const float* stats, const float* beta, long long V, float* y,
+                               hipStream_t stream);
+int mvs_refine_tail_bwd(const float* gy, const float* raw, const float* stats, const float* beta, int frozen, long long V, double* rec,
+                        float* draw, float* dgamma, float* dbeta, hipStream_t stream);
+int mvs_refine_tail_eval(const float* x, const float* w, const float* bias, const float* depth, float* y, int B, int h, int w_,
+                         hipStream_t stream);
+}
+
+static const int REFINE_CIN[4] = {4, 32, 32, 32}, REFINE_COUT[4] = {32, 32, 32, 1};
+
+static int refine_ptrs4(const char* what, const void* const* p, const char* name) {
+    MVS_REQUIRE(p, MVS_ERR_NULL, "%s: null pointer argument (%s)", what, name);
+    for (int i = 0; i < 4; ++i) MVS_REQUIRE(p[i], MVS_ERR_NULL, "%s: %s[%d] is null", what, name, i);
+    return MVS_OK;
+}
+#define REFINE_P4(what, p) MVS_TRY(refine_ptrs4(what, (const void* const*)(p), #p))
+
+extern "C" int mvs_refine_fwd(int frozen, int B, int H, int W, int h, int wd, const float* img, long long img_batch_stride, const float* depth,
+                              const float* const* w, const float* const* gamma, const float* const* beta, float* const* running_mean,
+                              float* const* running_var, const float* eps, const float* momentum, float* x0, float* const* packed,
+                              float* const* raw, float* y2, float* const* stats, double* const* slots, const int* nslots, float* out,
+                              hipStream_t stream) {
+    MVS_REQUIRE(img && depth && eps && momentum && x0 && y2 && nslots && out, MVS_ERR_NULL, "mvs_refine_fwd: null pointer argument");
+    REFINE_P4("mvs_refine_fwd", w); REFINE_P4("mvs_refine_fwd", gamma); REFINE_P4("mvs_refine_fwd", beta);
+    REFINE_P4("mvs_refine_fwd", running_mean); REFINE_P4("mvs_refine_fwd", running_var); REFINE_P4("mvs_refine_fwd", packed);
+    REFINE_P4("mvs_refine_fwd", raw); REFINE_P4("mvs_refine_fwd", stats); REFINE_P4("mvs_refine_fwd", slots);
+    MVS_TRY(mvs_refine_assemble(img, img_batch_stride, depth, x0, B, H, W, h, wd, stream));
+    const long long V = (long long)B * h * wd;
+    int shapes[16], wcl[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i) { shapes[4 * i] = REFINE_CIN[i]; shapes[4 * i + 1] = REFINE_COUT[i]; shapes[4 * i + 2] = 3; shapes[4 * i + 3] = 1; }
+    MVS_TRY(mvs_conv2d_pack_weights_batch(4, w, packed, shapes, wcl, stream));
+    if (frozen)
+        for (int i = 0; i < 4; ++i)
+            MVS_TRY(mvs_bn_frozen_stats(gamma[i], beta[i], running_mean[i], running_var[i], eps[i], REFINE_COUT[i], stats[i], stream));
+    for (int i = 0; i < 3; ++i) {
+        if (i == 0)
+            MVS_TRY(mvs_conv2d_fwd_stats(x0, w[0], raw[0], packed[0], slots[0], nslots[0], 1, B, h, wd, 4, 32, 3, 1, 1, stream));
+        else
+            MVS_TRY(mvs_conv2d_fwd_stats_xf(raw[i - 1], stats[i - 1], w[i], raw[i], packed[i], slots[i], nslots[i], 1, B, h, wd, 32, 32, 3, 1, 1,
+                                            stream));
+        if (frozen) continue;
+        if (i < 2)
+            MVS_TRY(mvs_bn_finalize_slots(slots[i], nslots[i], 1, V, 32, gamma[i], beta[i], eps[i], momentum[i], running_mean[i], running_var[i],
+                                          stats[i], stream));
+        else
+            MVS_TRY(mvs_bn_relu_fwd_slots(raw[2], slots[2], nslots[2], 1, V, 32, gamma[2], beta[2], eps[2], momentum[2], running_mean[2],
+                                          running_var[2], nullptr, 1, stats[2], y2, stream));
+    }
+    if (frozen) MVS_TRY(mvs_bn_relu_fwd(raw[2], stats[2] + 64, stats[2] + 96, nullptr, 1, V, 32, y2, stream));
+    MVS_TRY(mvs_conv2d_fwd_stats(y2, w[3], raw[3], packed[3], slots[3], nslots[3], 1, B, h, wd, 32, 1, 3, 1, 1, stream));
+    if (frozen) return mvs_refine_tail_fwd_frozen(raw[3], depth, stats[3], beta[3], V, out, stream);
+    return mvs_refine_tail_fwd(raw[3], depth, slots[3], nslots[3], V, gamma[3], beta[3], eps[3], momentum[3], running_mean[3], running_var[3],
+                               stats[3], out, stream);
+}
+
+// eval mode without a gradient: BatchNorm folded into the weights by the caller.  packed[3]: the forward weight images of the three
+// 32-channel blocks (mvs_conv2d_pack_weights_batch of the FOLDED weights, kept by the caller while the parameters do not change),
+// bias[3] their folded biases; wtail [1][32][3][3] / btail [1]: the folded 32 -> 1 layer.  5 launches.
+extern "C" int mvs_refine_eval_fwd(int B, int H, int W, int h, int wd, const float* img, long long img_batch_stride, const float* depth, float* const* packed,
+                                   const float* const* bias, const float* wtail, const float* btail, float* x0, float* buf_a, float* buf_b,
+                                   float* out, hipStream_t stream) {
+    MVS_REQUIRE(img && depth && packed && bias && wtail && btail && x0 && buf_a && buf_b && out, MVS_ERR_NULL,
+                "mvs_refine_eval_fwd: null pointer argument");
+    for (int i = 0; i < 3; ++i) MVS_REQUIRE(packed[i] && bias[i], MVS_ERR_NULL, "mvs_refine_eval_fwd: null weight image / bias of block %d", i);
+    MVS_TRY(mvs_refine_assemble(img, img_batch_stride, depth, x0, B, H, W, h, wd, stream));
+    MVS_TRY(mvs_conv2d_relu_fwd_packed(x0, packed[0], bias[0], buf_a, B, h, wd, 4, 32, stream));
+    MVS_TRY(mvs_conv2d_relu_fwd_packed(buf_a, packed[1], bias[1], buf_b, B, h, wd, 32, 32, stream));
+    MVS_TRY(mvs_conv2d_relu_fwd_packed(buf_b, packed[2], bias[2], buf_a, B, h, wd, 32, 32, stream));
+    return mvs_refine_tail_eval(buf_a, wtail, btail, depth, out, B, h, wd, stream);
+}
+
+// The reverse order.  gout [B,h,w]: gradient of the refined depth.  gbuf[3] / draw[0..2] [B,h,w,32], draw[3] [B,h,w], gx0 [B,h,w,4]:
+// work buffers; slots_b[3]: caller-zeroed backward statistic rows of the 32-channel blocks; tail_rec: 512 doubles of scratch.
+// Every weight gradient is computed: layers 1, 2 in one launch on the raw activations (mvs_conv2d_wgrad_batch_xf), the 4 -> 32 and
+// 32 -> 1 layers, which that launch has no instantiation for, through mvs_conv2d_wgrad.  gimg [B,3,H,W] or NULL; gdepth [B,h,w] =
+// gout (the residual's identity branch) + channel 3 of gx0.
+extern "C" int mvs_refine_bwd(int frozen, int B, int H, int W, int h, int wd, const float* const* w, const float* x0, const float* const* raw, const float* y2,
+                              const float* const* stats, const float* beta3, double* const* slots_b, const int* nslots, double* tail_rec,
+                              const float* gout, float* const* gbuf, float* const* draw, float* gx0, float* dgrad_ws, float* const* gw,
+                              float* wgrad_ws, float* const* dgamma, float* const* dbeta, float* gimg, float* gdepth, hipStream_t stream) {
+    MVS_REQUIRE(x0 && y2 && beta3 && nslots && tail_rec && gout && gx0 && dgrad_ws && wgrad_ws && gdepth && slots_b && gbuf, MVS_ERR_NULL,
+                "mvs_refine_bwd: null pointer argument");
+    REFINE_P4("mvs_refine_bwd", w); REFINE_P4("mvs_refine_bwd", raw); REFINE_P4("mvs_refine_bwd", stats); REFINE_P4("mvs_refine_bwd", draw);
+    REFINE_P4("mvs_refine_bwd", gw); REFINE_P4("mvs_refine_bwd", dgamma); REFINE_P4("mvs_refine_bwd", dbeta);
+    for (int i = 0; i < 3; ++i) MVS_REQUIRE(slots_b[i] && gbuf[i], MVS_ERR_NULL, "mvs_refine_bwd: null work buffer of block %d", i);
+    MVS_REQUIRE(B >= 1 && H >= 4 && W >= 4 && h == H / 4 && wd == W / 4, MVS_ERR_SHAPE, "mvs_refine_bwd: a [%d,3,%d,%d] image does not go with a [%d,%d,%d] depth map", B, H, W, B, h, wd);
+    const long long V = (long long)B * h * wd;
+    MVS_TRY(mvs_refine_tail_bwd(gout, raw[3], stats[3], beta3, frozen, V, tail_rec, draw[3], dgamma[3], dbeta[3], stream));
+    MVS_TRY(mvs_conv2d_dgrad_wl(draw[3], w[3], gbuf[2], dgrad_ws, B, h, wd, 32, 1, 3, 1, 0, stream));
+    for (int i = 2; i >= 0; --i) {
+        if (frozen) {
+            MVS_TRY(mvs_bn_relu_bwd_frozen(gbuf[i], raw[i], stats[i], slots_b[i], nslots[i], 0, 1, V, 32, draw[i], dgamma[i], dbeta[i], stream));
+        } else {
+            MVS_TRY(mvs_bn_bwd_reduce_slots(gbuf[i], raw[i], stats[i], 1, 1, V, 32, slots_b[i], nslots[i], stream));
+            MVS_TRY(mvs_bn_relu_bwd_slots(gbuf[i], raw[i], stats[i], slots_b[i], nslots[i], 1, 1, V, 32, draw[i], dgamma[i], dbeta[i], stream));
+        }
+        MVS_TRY(mvs_conv2d_dgrad_wl(draw[i], w[i], i > 0 ? gbuf[i - 1] : gx0, dgrad_ws, B, h, wd, REFINE_CIN[i], 32, 3, 1, 0, stream));
+    }
+    const float* xs[2] = {raw[0], raw[1]};
+    const float* xst[2] = {stats[0], stats[1]};
+    const float* gys[2] = {draw[1], draw[2]};
+    float* gws[2] = {gw[1], gw[2]};
+    const int shapes[16] = {B, h, wd, 32, 32, 3, 1, 0, B, h, wd, 32, 32, 3, 1, 0};
+    MVS_TRY(mvs_conv2d_wgrad_batch_xf(2, xs, xst, B, gys, gws, wgrad_ws, shapes, stream));
+    MVS_TRY(mvs_conv2d_wgrad(x0, draw[0], gw[0], wgrad_ws, B, h, wd, 4, 32, 3, 1, stream));
+    MVS_TRY(mvs_conv2d_wgrad(y2, draw[3], gw[3], wgrad_ws, B, h, wd, 32, 1, 3, 1, stream));
+    return mvs_refine_assemble_bwd(gx0, gout, gimg, gdepth, B, H, W, h, wd, stream);
+}

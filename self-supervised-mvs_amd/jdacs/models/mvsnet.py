@@ -4,7 +4,8 @@
 Hot path (HIP): plane-sweep variance volume (mvsnet.py:120-136 + module.py:105-140), CostRegNet
 (mvsnet.py:37-74), softmax + depth regression + confidence (mvsnet.py:141-151).
 FeatureNet / RefineNet are 2-D CNNs next to the path: they keep the reference's parameter names and run through
-csrc/conv2d.hip where that measured faster (eval: folded BatchNorm; training: ops.FeatureExtractorFn) and the library elsewhere."""
+csrc/conv2d.hip where that measured faster (eval: folded BatchNorm; training: ops.FeatureExtractorFn, ops.RefineNetFn) and the
+library elsewhere."""
 import os
 
 import torch
@@ -120,14 +121,81 @@ class CostRegNet(nn.Module):
 
 
 class RefineNet(nn.Module):
-    """mvsnet.py:77-92 (off by default in the reference, config.py:48): residual on the 1/4-resolution image + depth."""
+    """mvsnet.py:77-92 (off by default in the reference, config.py:48): residual on the 1/4-resolution image + depth.  In train mode
+    and under the freeze idiom the whole net is ONE autograd node with one C call per pass (``hip_pass``): no library kernel."""
+
+    # The whole net through this library's kernels, one autograd node / one C call per pass (ops.RefineNetFn, ops.refine_eval):
+    # True / False = every mode / none; None = the modes of HIP_PASS_DEFAULT_MODES, set from profiles/refine_timing.json by the rule of
+    # DESIGN.md section 7 (on only where the HIP pass's p90 is below the stock path's p10).  MVS_HIP_REFINE=1 / 0 sets it.
+    # Measured (tools/refine_bench.py): train and frozen win at both shapes (1.07 -> 0.64 ms, 1.01 -> 0.62 ms at 512x640); eval wins at
+    # 512x640 (0.139 -> 0.121 ms) but not by the rule at 864x1152 (0.141 -> 0.135 ms, HIP p90 0.140 above stock p10 0.138): opt-in.
+    hip_pass = {"1": True, "0": False}.get(os.environ.get("MVS_HIP_REFINE", ""), None)
+    HIP_PASS_DEFAULT_MODES = frozenset(("train", "frozen"))
+    _BLOCKS = (("conv1", 4, 32), ("conv2", 32, 32), ("conv3", 32, 32), ("res", 32, 1))
 
     def __init__(self):
         super().__init__()
-        for name, cin, cout in (("conv1", 4, 32), ("conv2", 32, 32), ("conv3", 32, 32), ("res", 32, 1)):
+        for name, cin, cout in self._BLOCKS:
             setattr(self, name, ConvBnReLU(cin, cout))
 
+    def hip_pass_mode(self, img, depth_init):
+        """"train" / "frozen" / "eval": the mode in which the one-node pass serves this call; None: the per-block path does (a mix of
+        BatchNorm modes, a tensor that is not fp32 on the library's device, momentum=None, a non-affine or untracked BatchNorm, a
+        block that is not the reference's, or a per-block switch -- ConvBnReLU.hip_conv, hip_bn = False -- asking for its own path)."""
+        from ... import _lib
+        if self.hip_pass is False:
+            return None
+        dev_type = "cuda" if _lib._INSTANCE is None else _lib._INSTANCE.device_type
+        for t in (img, depth_init):
+            if t.device.type != dev_type or t.dtype != torch.float32:
+                return None
+        if img.dim() != 4 or img.shape[1] != 3 or depth_init.dim() != 3:
+            return None
+        blocks = [getattr(self, name) for name, *_ in self._BLOCKS]
+        for m, (_, cin, cout) in zip(blocks, self._BLOCKS):
+            c, bn = m.conv, m.bn
+            if (type(m) is not ConvBnReLU or m.hip_conv or not m.hip_bn or tuple(c.weight.shape) != (cout, cin, 3, 3) or c.bias is not None
+                    or c.stride != (1, 1) or c.padding != (1, 1) or c.dilation != (1, 1) or c.groups != 1 or not c.weight.is_contiguous()
+                    or c.weight.dtype != torch.float32 or not bn.affine or not bn.track_running_stats or bn.running_mean is None
+                    or bn.momentum is None):
+                return None
+        mode = ops.unet_bn_mode(m.bn for m in blocks)
+        if mode == "frozen" and not torch.is_grad_enabled():
+            mode = "eval" if ConvBnReLU.fold_eval else None
+        elif mode == "mixed":
+            mode = None
+        if mode is not None and self.hip_pass is None and mode not in self.HIP_PASS_DEFAULT_MODES:
+            return None
+        return mode
+
+    def _eval_images(self, like):
+        """the folded weights as mvs_refine_eval_fwd takes them, rebuilt only when a block's folded weights were (ConvBnReLU._folded)"""
+        folded = [getattr(self, name)._folded() for name, *_ in self._BLOCKS]
+        key = tuple(id(f[0]) for f in folded)
+        cache = self.__dict__.get("_eval_cache")
+        if cache is None or cache[0] != key:
+            packed = ops.pack_conv2d_weights([f[0] for f in folded[:3]], [1, 1, 1], like)
+            cache = (key, folded, packed, [f[1] for f in folded[:3]], folded[3][0], folded[3][1])
+            self.__dict__["_eval_cache"] = cache
+        return cache[2:]
+
+    def __getstate__(self):
+        state = dict(self.__dict__)                      # deepcopy / pickle: the cache is derived data
+        state.pop("_eval_cache", None)
+        return state
+
     def forward(self, img, depth_init):
+        mode = self.hip_pass_mode(img, depth_init)
+        if mode == "eval":
+            return ops.refine_eval(img, depth_init, *self._eval_images(depth_init))
+        if mode is not None:
+            cfg, params = [], []
+            for name, *_ in self._BLOCKS:
+                m = getattr(self, name)
+                count_batch(m.bn, mode == "train")
+                cfg.append((float(m.bn.eps), float(m.bn.momentum)))
+                params += [m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var]
+            return ops.RefineNetFn.apply(img, depth_init, mode == "frozen", tuple(cfg), *params)
         small = F.interpolate(img, scale_factor=0.25, mode='bilinear')
         d = depth_init.unsqueeze(1)
         x = torch.cat((small, d), dim=1)

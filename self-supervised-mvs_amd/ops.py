@@ -1787,6 +1787,168 @@ class FeatureExtractorFn(torch.autograd.Function):
         return (g if need[0] else None, None, None) + tuple(grads)
 
 
+# ---- RefineNet (jdacs/models/mvsnet.py:77-92) as one autograd node: csrc/refine_kernels.h + mvs_refine_fwd / _bwd -------------------
+_REFINE_CH = ((4, 32), (32, 32), (32, 32), (32, 1))
+_REFINE_TAIL_SLOTS = 128          # statistic rows of the one-channel block (a power of two <= 256; the tail sums them in its prologue)
+_REFINE_PLANS = {}
+
+
+class _RefinePlan:
+    """What is the same for every step at one (B, H, W): the arena offsets (floats / doubles) of mvs_refine_fwd / _bwd's buffers."""
+
+    def __init__(self, lib, B, H, W):
+        h, w = H // 4, W // 4
+        self.B, self.H, self.W, self.h, self.w = B, H, W, h, w
+        V = B * h * w
+        al = lambda v: (v + 63) // 64 * 64
+        ws_f = lambda op, ci, co: int(lib.raw("mvs_conv2d_workspace_floats", op, B, h, w, ci, co, 3, 1))
+        # forward arena: x0, raw0..2, y2, raw3, stats0..3, the four forward weight images
+        off = 0
+        self.x0_off = off; off += al(4 * V)
+        self.raw_off = []
+        for i in range(3):
+            self.raw_off.append(off); off += al(32 * V)
+        self.y2_off = off; off += al(32 * V)
+        self.raw_off.append(off); off += al(V)
+        self.stats_off = []
+        for ci, co in _REFINE_CH:
+            self.stats_off.append(off); off += al(4 * co)
+        self.packed_off = []
+        for ci, co in _REFINE_CH:
+            self.packed_off.append(off); off += al(ws_f(0, ci, co))
+        self.fwd_floats = off
+        # statistic rows (doubles): forward rows of the four blocks, backward rows of the three 32-channel ones
+        n32 = bn_nslots(lib, 32)
+        self.nslots = (C.c_int * 4)(n32, n32, n32, _REFINE_TAIL_SLOTS)
+        soff = 0
+        self.sf_off, self.sb_off = [], []
+        for i, (ci, co) in enumerate(_REFINE_CH):
+            self.sf_off.append(soff); soff += self.nslots[i] * 2 * co
+        for i in range(3):
+            self.sb_off.append(soff); soff += n32 * 2 * 32
+        self.slot_doubles = soff
+        # backward work arena: gbuf0..2, draw0..3, gx0, the input gradients' weight image, the weight gradients' partial images
+        off = 0
+        self.g_off, self.draw_off = [], []
+        for i in range(3):
+            self.g_off.append(off); off += al(32 * V)
+        for i in range(4):
+            self.draw_off.append(off); off += al(32 * V if i < 3 else V)
+        self.gx0_off = off; off += al(4 * V)
+        self.dgws_off = off; off += al(max(ws_f(1, ci, co) for ci, co in _REFINE_CH))
+        rows = [B, h, w, 32, 32, 3, 1, 0] * 2
+        wg = max(ws_f(2, 4, 32), ws_f(2, 32, 1), int(lib.raw("mvs_conv2d_wgrad_batch_workspace_floats", 2, (C.c_int * 16)(*rows))))
+        self.wgws_off = off; off += al(wg)
+        self.bwd_floats = off
+        self.V = V
+
+
+def _refine_plan(lib, B, H, W):
+    key = (id(lib), B, H, W)
+    plan = _REFINE_PLANS.get(key)
+    if plan is None:
+        if len(_REFINE_PLANS) > 16:
+            _REFINE_PLANS.clear()
+        plan = _REFINE_PLANS[key] = _RefinePlan(lib, B, H, W)
+    return plan
+
+
+def _refine_inputs(img, depth):
+    """the image as the kernels read it: fp32 [B,3,H,W] with contiguous [3,H,W] images at any batch stride (a view such as
+    imgs[:, 0] of [B,N,3,H,W] is read in place); depth [B,h,w] contiguous"""
+    if img.dim() != 4 or img.shape[1] != 3 or depth.dim() != 3 or depth.shape[0] != img.shape[0]:
+        raise ValueError("mvs_amd RefineNet: image [B,3,H,W] and depth [B,H/4,W/4] expected, got %s and %s" % (tuple(img.shape), tuple(depth.shape)))
+    B, _, H, W = img.shape
+    if tuple(img.stride()[1:]) != (H * W, W, 1) or (B > 1 and img.stride(0) < 3 * H * W):
+        img = img.contiguous()
+    return img, depth.contiguous(), (img.stride(0) if B > 1 else 3 * H * W)
+
+
+class RefineNetFn(torch.autograd.Function):
+    """RefineNet (jdacs/models/mvsnet.py:77-92) as ONE autograd node, one C call per pass (mvs_refine_fwd / mvs_refine_bwd): bilinear
+    quarter-size image || depth -> ConvBnReLU 4 -> 32 -> 32 -> 32 -> 1 -> + depth, every kernel this library's.
+
+    ``frozen``: False -- every BatchNorm takes batch statistics and moves its running statistics (``cfg``: per block (eps, momentum));
+    True -- every one normalises with its running statistics, which nothing writes.  ``params``: per block conv weight (contiguous),
+    gamma, beta, running_mean, running_var.  The image may be a view with its own batch stride; it gets a gradient only if it asks."""
+
+    @staticmethod
+    def forward(ctx, img, depth, frozen, cfg, *params):
+        lib = _lib_for(depth)
+        _lib_for(img)
+        img, depth, bstride = _refine_inputs(img, depth)
+        B, _, H, W = img.shape
+        plan = _refine_plan(lib, B, H, W)
+        dev = depth.device
+        ws_ = [params[5 * i] for i in range(4)]
+        for w_, (ci, co) in zip(ws_, _REFINE_CH):
+            if tuple(w_.shape) != (co, ci, 3, 3) or not w_.is_contiguous():
+                raise ValueError("mvs_amd RefineNetFn: contiguous [%d,%d,3,3] weight expected, got %s" % (co, ci, tuple(w_.shape)))
+        arena = torch.empty(max(1, plan.fwd_floats), dtype=torch.float32, device=dev)
+        (slots,) = stat_slots(depth, 1, 1, plan.slot_doubles // 2 + 1, 1)
+        out = torch.empty((B,) + tuple(depth.shape[1:]), dtype=torch.float32, device=dev)
+        ab, sb = arena.data_ptr(), slots.data_ptr()
+        eps = (C.c_float * 4)(*[float(c[0]) for c in cfg])
+        mom = (C.c_float * 4)(*[float(c[1]) for c in cfg])
+        lib.call("mvs_refine_fwd", int(bool(frozen)), B, H, W, int(depth.shape[1]), int(depth.shape[2]), _p(img), bstride, _p(depth), _ptr_array(ws_),
+                 _ptr_array([params[5 * i + 1] for i in range(4)]), _ptr_array([params[5 * i + 2] for i in range(4)]),
+                 _ptr_array([params[5 * i + 3] for i in range(4)]), _ptr_array([params[5 * i + 4] for i in range(4)]), eps, mom,
+                 ab + 4 * plan.x0_off, _ptrs(ab, plan.packed_off), _ptrs(ab, plan.raw_off), ab + 4 * plan.y2_off, _ptrs(ab, plan.stats_off),
+                 _ptrs(sb, plan.sf_off, 8), plan.nslots, _p(out), _stream(depth))
+        ctx.frozen, ctx.plan, ctx.slots_used = bool(frozen), plan, False
+        ctx.save_for_backward(arena, slots, params[5 * 3 + 2], *ws_)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        plan = ctx.plan
+        arena, slots, beta3 = ctx.saved_tensors[:3]
+        ws_ = ctx.saved_tensors[3:7]
+        lib = _lib_for(arena)
+        dev = arena.device
+        if ctx.slots_used:                       # a second backward through the same graph: fresh backward accumulators
+            slots = torch.zeros_like(slots)
+        ctx.slots_used = True
+        gout = gout.contiguous()
+        B, H, W = plan.B, plan.H, plan.W
+        work = torch.empty(plan.bwd_floats, dtype=torch.float32, device=dev)
+        rec = torch.empty(512, dtype=torch.float64, device=dev)
+        dgb = torch.empty(2 * (32 * 3 + 1), dtype=torch.float32, device=dev)
+        gws = [torch.empty_like(w_) for w_ in ws_]
+        gimg = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        gdepth = torch.empty_like(gout)
+        ab, sb, wb, db = arena.data_ptr(), slots.data_ptr(), work.data_ptr(), dgb.data_ptr()
+        goff = [0, 64, 128, 192]                 # (dgamma_i, dbeta_i) pairs: 32 + 32 floats per 32-channel block, 1 + 1 for the last
+        lib.call("mvs_refine_bwd", int(ctx.frozen), B, H, W, plan.h, plan.w, _ptr_array(ws_), ab + 4 * plan.x0_off, _ptrs(ab, plan.raw_off),
+                 ab + 4 * plan.y2_off, _ptrs(ab, plan.stats_off), _p(beta3), _ptrs(sb, plan.sb_off, 8), plan.nslots, _p(rec), _p(gout),
+                 _ptrs(wb, plan.g_off), _ptrs(wb, plan.draw_off), wb + 4 * plan.gx0_off, wb + 4 * plan.dgws_off, _ptr_array(gws),
+                 wb + 4 * plan.wgws_off, _ptrs(db, goff), _ptrs(db, [o + (32 if i < 3 else 1) for i, o in enumerate(goff)]), _p(gimg),
+                 _p(gdepth), _stream(arena))
+        grads = []
+        for i in range(4):
+            c = 32 if i < 3 else 1
+            grads += [gws[i], dgb[goff[i]:goff[i] + c], dgb[goff[i] + c:goff[i] + 2 * c], None, None]
+        return (gimg, gdepth, None, None) + tuple(grads)
+
+
+def refine_eval(img, depth, packed, biases, wtail, btail):
+    """RefineNet in eval mode without a gradient, BatchNorm folded into the weights by the caller: 5 launches (mvs_refine_eval_fwd).
+    packed / biases: pack_conv2d_weights() images and folded biases of the three 32-channel blocks; wtail [1,32,3,3] / btail [1]."""
+    lib = _lib_for(depth)
+    _lib_for(img)
+    img, depth, bstride = _refine_inputs(img, depth)
+    B, _, H, W = img.shape
+    h, w = H // 4, W // 4
+    V = B * h * w
+    al = lambda v: (v + 63) // 64 * 64
+    arena = torch.empty(al(4 * V) + 2 * al(32 * V), dtype=torch.float32, device=depth.device)
+    out = torch.empty_like(depth)
+    ab = arena.data_ptr()
+    lib.call("mvs_refine_eval_fwd", B, H, W, int(depth.shape[1]), int(depth.shape[2]), _p(img), bstride, _p(depth), _ptr_array(packed), _ptr_array(biases), _p(wtail), _p(btail),
+             ab, ab + 4 * al(4 * V), ab + 4 * (al(4 * V) + al(32 * V)), _p(out), _stream(depth))
+    return out
+
+
 class BnReLUFn(torch.autograd.Function):
     """BatchNorm (+ReLU) over the channel dim of a channels-last tensor [B,C,H,W] / [B,C,D,H,W] with the same
     HIP kernels as the 3-D regulariser (statistic slots -> ONE apply pass that finishes them in its prologue; backward: one
