@@ -292,6 +292,33 @@ int mvs_sample_prep(const void* src, int src_kind, long long src_image_stride, c
                     float* imgs_aug, float* imgs_seg, float* filter_mask, int mask_scale, int aug_center, int channels_last, int M,
                     int H, int W, void* ws, hipStream_t stream);
 
+/* ---- The optimiser step: Adam over the flat parameter store, one launch (csrc/adam_kernels.h) --------------------------------
+ * Replaces optim.Adam(model.parameters(), lr, betas=(0.9, 0.999), weight_decay=wd).step() of jdacs/train.py:71,208 and
+ * jdacs-ms/train.py:101,260 for parameters that are views of ONE flat fp32 store (dist.FlatGradBucket(flatten_params=True)).
+ * For element i, all fp32:  g = grad[i] * grad_scale (+ weight_decay * p[i] when weight_decay != 0: torch's L2 form, not AdamW);
+ *   m[i] += (1 - beta1) (g - m[i]);  v[i] = beta2 v[i] + (1 - beta2) g g;  p[i] -= (lr / bc1) m[i] / (sqrt(v[i]) / sqrt(bc2) + eps)
+ * with bc = 1 - beta^t; the constants are formed in fp64 and rounded to fp32 once.  grad_scale carries the 1/world of a summed
+ * all-reduce.  p, m, v: flat [n] device arrays, updated in place; 16-byte accesses where the actual addresses allow, any alignment
+ * and any n work.
+ * step_counter: device int[2], owned by the optimiser: [0] = steps taken so far, [1] = scratch that is 0 between calls (zero both
+ * to start).  The step t = [0] + 1 is read on the device and [0] is advanced by exactly 1 per call, so a launch captured into a
+ * graph stays correct on replay; lr and the other hyper-parameters are arguments and ARE baked into a captured launch.
+ * mvs_adam_step: grad flat [n] (the packed bucket).  One launch, trace label "adam_flat".
+ * mvs_adam_step_table: the gradient of flat range [offsets[k], offsets[k] + counts[k]) is read from grads[k] (HOST arrays of nseg
+ *   entries; grads[k] a device pointer of counts[k] floats with 4-byte alignment, or NULL = a gradient of zeros).  Segments must be
+ *   sorted by offset, non-empty, disjoint and inside [0, n); elements that no segment covers are left untouched.  The table travels
+ *   in the kernel arguments: one launch ("adam_table") per MVS_ADAM_MAX_SEGMENTS = 128 segments, earlier launches of a longer table
+ *   are labelled "adam_table part" and only the last advances the counter.  Bit-identical to mvs_adam_step on the packed gradients.
+ * mvs_adam_limits: the workgroup's chunk of flat elements and the segments per launch (for tests of the boundary cases).
+ * Checked on the host before any launch: null pointers, n <= 0 (MVS_ERR_SHAPE) or n above 2^31 - 2049 (MVS_ERR_UNSUPPORTED), the
+ * segment rules, lr < 0, betas outside [0, 1), eps < 0, weight_decay < 0, non-finite hyper-parameters. */
+int mvs_adam_limits(int* chunk, int* max_segments);
+int mvs_adam_step(float* p, const float* grad, float* m, float* v, long long n, int* step_counter, double lr, double beta1,
+                  double beta2, double eps, double weight_decay, double grad_scale, hipStream_t stream);
+int mvs_adam_step_table(float* p, float* m, float* v, long long n, const float* const* grads, const long long* offsets,
+                        const long long* counts, int nseg, int* step_counter, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, double grad_scale, hipStream_t stream);
+
 /* ---- K9/K10: softmax over depth + soft-argmin regression + photometric confidence --------------
  * Replace F.softmax(dim=1) + depth_regression + the pad/avg_pool3d/gather confidence:
  *   jdacs/models/mvsnet.py:141-151, jdacs/models/module.py:145-148;

@@ -103,6 +103,9 @@ SIGNATURES = {
     "mvs_depth_metrics": (_i, [_f, _f, _f, _i, _f, C.POINTER(_fl), _i, _i, _i, _f, _f, _f, _f, _f, _s]),
     "mvs_sample_prep_workspace_bytes": (_ll, [_i, _i, _i]),
     "mvs_sample_prep": (_i, [_f, _i, _ll, C.POINTER(_fl), C.POINTER(_i), _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _f, _s]),
+    "mvs_adam_limits": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "mvs_adam_step": (_i, [_f, _f, _f, _f, _ll, _f] + [C.c_double] * 6 + [_s]),
+    "mvs_adam_step_table": (_i, [_f, _f, _f, _ll, _pp, C.POINTER(_ll), C.POINTER(_ll), _i, _f] + [C.c_double] * 6 + [_s]),
     "mvs_softargmin_conf_fwd": (_i, [_f, _f, _i, _i, _i, _i, _i, _f, _f, _f, _f, _s]),
     "mvs_softargmin_conf_bwd": (_i, [_f, _f, _f, _i, _f, _f, _f, _i, _i, _i, _i, _f, _s]),
     "mvs_conv2d_workspace_floats": (_ll, [_i] * 8),

@@ -64,3 +64,4 @@ extern "C" int mvs_masked_smooth_l1_bwd(const float* est, const float* gt, const
 
 #include "depth_metrics_kernels.h"   // the seven validation metrics of the same (est, gt, mask) maps: mvs_depth_metrics
 #include "sample_prep_kernels.h"     // the step's input tensors from the decoded u8 views: mvs_sample_prep
+#include "adam_kernels.h"            // the optimiser step over the flat parameter store: mvs_adam_step, mvs_adam_step_table

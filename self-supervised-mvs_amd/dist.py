@@ -185,10 +185,15 @@ class FlatGradBucket:
 
     force_collective = False    # True: run the collective at world size 1 as well (bench.py --force-collective)
 
-    def all_reduce(self) -> None:
-        if dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or self.force_collective):
+    def needs_collective(self) -> bool:
+        return dist.is_available() and dist.is_initialized() and (dist.get_world_size() > 1 or self.force_collective)
+
+    def all_reduce(self, average: bool = True) -> None:
+        """average=False leaves the SUM over the ranks in the bucket: the caller folds 1/world into what it does next
+        (optim.FlatAdam passes it to the update kernel as grad_scale and saves the divide's launch)."""
+        if self.needs_collective():
             _all_reduce_sum(self.flat)
-            if dist.get_world_size() > 1:
+            if average and dist.get_world_size() > 1:
                 self.flat.div_(dist.get_world_size())
 
 

@@ -2363,6 +2363,69 @@ def depth_metrics(est, gt, mask, interval=None, thresholds=(2, 4, 8), meter=None
 
 
 # ------------------------------------------------------------------------------------------------
+# The optimiser step over the flat parameter store (csrc/adam_kernels.h); optim.FlatAdam is the optimiser built on these
+# ------------------------------------------------------------------------------------------------
+def adam_limits(lib=None):
+    """(chunk, max_segments): flat elements per workgroup and table rows per launch of the Adam kernels."""
+    lib = lib or _lib.get()
+    chunk, segs = C.c_int(), C.c_int()
+    lib.call("mvs_adam_limits", C.byref(chunk), C.byref(segs))
+    return chunk.value, segs.value
+
+
+def _adam_flat_args(what, p, m, v, counter):
+    lib = _lib_for(p)
+    for name, t in (("p", p), ("exp_avg", m), ("exp_avg_sq", v)):
+        _lib_for(t)
+        if t.dim() != 1 or not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
+            raise ValueError("%s: %s must be a contiguous 1-D tensor of %d elements on %s, got shape %s strides %s on %s"
+                             % (what, name, p.numel(), p.device, tuple(t.shape), t.stride(), t.device))
+    if counter.dtype != torch.int32 or counter.numel() != 2 or not counter.is_contiguous() or counter.device != p.device:
+        raise ValueError("%s: counter must be a contiguous int32 [2] tensor on %s (steps taken, scratch), got %s %s on %s"
+                         % (what, p.device, counter.dtype, tuple(counter.shape), counter.device))
+    return lib
+
+
+def adam_step(p, grad, exp_avg, exp_avg_sq, counter, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, grad_scale=1.0):
+    """One Adam step (torch.optim.Adam's arithmetic, L2 weight decay) on the flat fp32 tensors p, exp_avg, exp_avg_sq [n] from the
+    flat gradient grad [n] times grad_scale, in place, as one launch.  counter: int32 [2] on the device, zeros to start; counter[0]
+    is the number of steps taken and is advanced on the device (mvs_adam_step in include/mvs_hip.h)."""
+    lib = _adam_flat_args("adam_step", p, exp_avg, exp_avg_sq, counter)
+    _lib_for(grad)
+    if grad.dim() != 1 or not grad.is_contiguous() or grad.numel() != p.numel() or grad.device != p.device:
+        raise ValueError("adam_step: grad must be a contiguous 1-D tensor of %d elements on %s, got shape %s on %s"
+                         % (p.numel(), p.device, tuple(grad.shape), grad.device))
+    lib.call("mvs_adam_step", _p(p), _p(grad), _p(exp_avg), _p(exp_avg_sq), p.numel(), _p(counter), float(lr), float(betas[0]),
+             float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _stream(p))
+
+
+def adam_step_table(p, grads, offsets, counts, exp_avg, exp_avg_sq, counter, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+                    grad_scale=1.0):
+    """The same step with the gradient of flat range [offsets[k], offsets[k] + counts[k]) read from grads[k] where it lies: an
+    fp32 tensor of counts[k] elements, dense (its elements are taken in the order they lie in memory), or None for a gradient of
+    zeros.  Segments sorted by offset and disjoint; elements outside every segment are left untouched.  One launch per
+    adam_limits()[1] segments; the results are bit-identical to adam_step on the packed gradients (mvs_adam_step_table)."""
+    lib = _adam_flat_args("adam_step_table", p, exp_avg, exp_avg_sq, counter)
+    nseg = len(grads)
+    if nseg != len(offsets) or nseg != len(counts):
+        raise ValueError("adam_step_table: %d gradients, %d offsets, %d counts" % (nseg, len(offsets), len(counts)))
+    from .dist import FlatGradBucket
+    ptrs = (C.c_void_p * max(nseg, 1))()
+    for k, g in enumerate(grads):
+        if g is None:
+            continue
+        _lib_for(g)
+        if g.device != p.device or g.numel() != int(counts[k]) or not FlatGradBucket._is_dense(g):
+            raise ValueError("adam_step_table: gradient %d must be a dense tensor of %d elements on %s, got shape %s strides %s on %s"
+                             % (k, int(counts[k]), p.device, tuple(g.shape), g.stride(), g.device))
+        ptrs[k] = g.data_ptr()
+    offs = (C.c_longlong * max(nseg, 1))(*[int(o) for o in offsets])
+    cnts = (C.c_longlong * max(nseg, 1))(*[int(c) for c in counts])
+    lib.call("mvs_adam_step_table", _p(p), _p(exp_avg), _p(exp_avg_sq), p.numel(), ptrs, offs, cnts, nseg, _p(counter), float(lr),
+             float(betas[0]), float(betas[1]), float(eps), float(weight_decay), float(grad_scale), _stream(p))
+
+
+# ------------------------------------------------------------------------------------------------
 # Training-sample preparation: the step's image tensors from the decoded u8 views (csrc/sample_prep_kernels.h)
 # ------------------------------------------------------------------------------------------------
 def sample_prep(src, table=None, rects=None, imgs=True, seg=True, mask_scale=None, aug_center=True, channels_last=False):
