@@ -155,13 +155,22 @@ __device__ __forceinline__ void bn_block_to_slot(float (&v)[8], float* red, int 
 #pragma unroll
     for (int k = 0; k < 8; ++k) r[k] = v[k];
     __syncthreads();
-    // threads [0, 2*C): stat = t / C, channel = t % C; sum over the 256/cq threads that own that quad
+    // threads [0, 2*C): stat = t / C, channel = t % C; sum over the 256/cq threads that own that quad.  In fp64, four chains in a
+    // fixed order (256/cq is 16 ... 256): one fp32 chain over 256 partial sums of x^2 lost what the fp64 slots were introduced to
+    // keep -- at |mean|/std = 32 it was the largest term of the variance's error, above what plain fp32 sums of x and x^2 give
+    // (tests/bn_train_cases.py, conditioning sweep).  Only the per-thread partial sums remain fp32.
     if (tid < 2 * C) {
         const int stat = tid / C, ch = tid % C;
         const int q = ch / 4, k = ch % 4;
-        float s = 0.f;
-        for (int t = q; t < 256; t += cq) s += red[t * 8 + stat * 4 + k];
-        MVS_GLOBAL_ATOMIC_ADD_F64(slot_row + tid, (double)s);
+        const float* r0 = red + stat * 4 + k;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (int t = q; t < 256; t += 4 * cq) {
+            s0 += (double)r0[t * 8];
+            s1 += (double)r0[(t + cq) * 8];
+            s2 += (double)r0[(t + 2 * cq) * 8];
+            s3 += (double)r0[(t + 3 * cq) * 8];
+        }
+        MVS_GLOBAL_ATOMIC_ADD_F64(slot_row + tid, (s0 + s1) + (s2 + s3));
     }
 }
 
