@@ -584,6 +584,62 @@ int mvs_refine_bwd(int frozen, int B, int H, int W, int h, int w_, const float* 
                    const float* gout, float* const* gbuf, float* const* draw, float* gx0, float* dgrad_ws, float* const* gw,
                    float* wgrad_ws, float* const* dgamma, float* const* dbeta, float* gimg, float* gdepth, hipStream_t stream);
 
+/* ---- FeaturePyramid of CVP-MVSNet in training as one autograd node (csrc/pyramid_kernels.h, csrc/conv2d.hip, csrc/feature_pass.cpp)
+ * jdacs-ms/models/network.py:16-50: nine conv 3x3 + bias + LeakyReLU blocks (3 -> 64 -> 64 -> 64 -> 32 -> 32 -> 32 -> 16 -> 16 -> 16)
+ * with the same weights on S <= 6 levels of a half-size image pyramid, h_0 = H, h_s = floor(h_{s-1} / 2); all views are one batch
+ * of N images.  Every tensor is channels-last fp32, 16-byte aligned.  One stream; nothing is allocated, no host synchronisation, no
+ * events, no atomics: two passes give the same bits.  Launch labels: "pyramid_images", "conv2d_pack_weights_batch",
+ * "conv2d_igemm k3 ccN nbN" (forward), "conv2d_pack_dgrad_weights_batch", "pyramid_head_mask", "conv2d_igemm k3 ccN nbN lrelu-mask"
+ * (cc16 / cc32, nb1 / nb2), "conv2d_wgrad k3 cxpN nbN" + "conv2d_wgrad_reduce wide|narrow", "pyramid_grad_finish".
+ * mvs_pyramid_images: img [N,3,H,W] contiguous -> out[s] [N,h_s,w_s,3] for s = 0 .. S-1 in ONE launch.  Level 0 is the layout change;
+ *   a pixel of level s is the half-size bilinear resize (F.interpolate(scale_factor=0.5), no align_corners) of level s-1, evaluated
+ *   as 0.5 * (0.5 * a + 0.5 * b) + 0.5 * (0.5 * c + 0.5 * d) (a, b the upper row's pair, c, d the lower row's) from its 2^s x 2^s
+ *   block of img.  A level with a side below one pixel: MVS_ERR_SHAPE.  No backward (the reference detaches the resized levels; a caller that wants
+ *   level 0's gradient towards the images takes the per-layer path).
+ * mvs_pyramid_record_rows(N, H, W): rows of a level's record buffers = workgroups of the masked input gradient (8 x 32 pixel tiles).
+ * mvs_conv2d_lrelu_fwd_packed: mvs_conv2d_lrelu_fwd with the forward weight image already in `packed`
+ *   (mvs_conv2d_pack_weights_batch): no pack launch.
+ * mvs_conv2d_pack_dgrad_weights_batch: the input-gradient weight images (transposed, flipped) of n <= 16 3x3 stride-1 layers in ONE
+ *   launch; shapes[n][2] = the layer's Cin, Cout; ws[i] >= mvs_conv2d_workspace_floats(1, ..., Cin, Cout, 3, 1) floats.
+ * mvs_conv2d_dgrad_lrelu_mask: gx [N,H,W,Cin] = mvs_conv2d_dgrad(gy [N,H,W,Cout]) * (y_front > 0 ? 1 : slope) -- the complete output
+ *   gradient of the conv + LeakyReLU block in front, whose saved output y_front [N,H,W,Cin] is (slope > 0) -- and
+ *   rec [mvs_pyramid_record_rows(N,H,W)][Cin] = per-workgroup channel sums of gx (plain stores, every row written: no zeroing).  More
+ *   than 8 channels on both sides (9..32 or 64).  ws_packed: ws holds the image of mvs_conv2d_pack_dgrad_weights_batch; w is not read.
+ * mvs_pyramid_head_mask: g = gout * (y > 0 ? 1 : slope) over [N,H,W,C], C in {4, 8, 16, 32, 64}, and rec as above (float4,
+ *   grid-stride loop, one workgroup per record row).
+ * mvs_pyramid_grad_finish: ONE launch for nlayers <= 9 layers.  slots / rec: [nlevels][nlayers] tables (row-major) of weight-gradient
+ *   images [Cout][Cin][3][3] and record buffers [rows[level]][Cout]; a NULL entry contributes nothing.  gw[i] = the sum over levels,
+ *   level 0 first, in fp64, rounded once, written in the parameter's memory layout ([Cout][3][3][Cin] when w_channels_last[i]);
+ *   gb[i] = the fp64 sum of layer i's records over rows and levels in a fixed order, rounded once.  A NULL gw[i] / gb[i] is skipped.
+ * mvs_pyramid_workspace_floats(N, H, W, S): floats of the `ws` of the two passes (forward and input-gradient weight images, two
+ *   ping-pong gradient buffers of the largest level, the per-level weight-gradient slots and record buffers, the partial images of
+ *   mvs_conv2d_wgrad -- asked for right before the call: it follows the "wgrad2d_groups" knob); -1 where a shape is not served.
+ * mvs_pyramid_fwd: imgs[s] [N,h_s,w_s,3] and act[s * 9 + i] [N,h_s,w_s,Cout_i] are the caller's (kept for the backward pass;
+ *   act[s * 9 + 8] is level s's feature map).  w[i] / bias[i]: the nine blocks' parameters, w_channels_last[i] as above.  Launches:
+ *   pyramid_images, one pack launch, 9 S convolutions.  Uses only the forward weight images of ws.
+ * mvs_pyramid_bwd: gout[s] [N,h_s,w_s,16] or NULL (such a level contributes nothing and launches nothing) -> gw[9], gb[9] (a NULL
+ *   entry is not computed).  Launches: one pack launch; per level the head, then from layer 8 down to 1 the layer's mvs_conv2d_wgrad
+ *   (into its slot of ws) and its masked input gradient into the other ping-pong buffer, then layer 0's weight gradient; one finish.
+ * Both check the chain and the levels before the first launch (MVS_ERR_SHAPE / MVS_ERR_UNSUPPORTED / MVS_ERR_NULL with a message). */
+int mvs_pyramid_images(const float* img, float* const* out, int N, int H, int W, int S, hipStream_t stream);
+int mvs_pyramid_record_rows(int N, int H, int W);
+int mvs_conv2d_lrelu_fwd_packed(const float* x, float* packed, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                                float negative_slope, hipStream_t stream);
+int mvs_conv2d_pack_dgrad_weights_batch(int n, const float* const* w, float* const* ws, const int* shapes, const int* w_channels_last,
+                                        hipStream_t stream);
+int mvs_conv2d_dgrad_lrelu_mask(const float* gy, const float* w, const float* y_front, float* gx, float* rec, float* ws, int N, int H, int W,
+                                int Cin, int Cout, float slope, int w_channels_last, int ws_packed, hipStream_t stream);
+int mvs_pyramid_head_mask(const float* gout, const float* y, float* g, float* rec, int N, int H, int W, int C, float slope,
+                          hipStream_t stream);
+int mvs_pyramid_grad_finish(int nlayers, const int* cin, const int* cout, const int* w_channels_last, int nlevels,
+                            const float* const* slots, const float* const* rec, const int* rows, float* const* gw, float* const* gb,
+                            hipStream_t stream);
+long long mvs_pyramid_workspace_floats(int N, int H, int W, int S);
+int mvs_pyramid_fwd(int S, int N, int H, int W, const float* img, const float* const* w, const float* const* bias,
+                    const int* w_channels_last, float slope, float* const* imgs, float* const* act, float* ws, hipStream_t stream);
+int mvs_pyramid_bwd(int S, int N, int H, int W, const float* const* w, const int* w_channels_last, float slope, const float* const* imgs,
+                    const float* const* act, const float* const* gout, float* const* gw, float* const* gb, float* ws, hipStream_t stream);
+
 /* ---- Wide forward 2-D convolutions: the frozen VGG-style trunk in front of the NMF (csrc/conv2d_wide_kernels.h) -----------------
  * 3x3, stride 1, pad 1, fp32, forward only, channels-last images x [N,H,W,Cin] -> y [N,H,W,Cout]; Cin = 3 or 32..512 and
  * Cout = 32..512 in steps of 32 (the existing mvs_conv2d_* family serves 1..32 or exactly 64 channels).  Implicit GEMM on the

@@ -60,6 +60,16 @@ SIGNATURES = {
     "mvs_refine_eval_fwd": (_i, [_i, _i, _i, _i, _i, _f, _ll, _f, _pp, _pp, _f, _f, _f, _f, _f, _f, _s]),
     "mvs_refine_bwd": (_i, [_i, _i, _i, _i, _i, _i, _pp, _f, _pp, _f, _pp, _f, _pp, C.POINTER(_i), _f, _f, _pp, _pp, _f, _f, _pp, _f, _pp, _pp, _f,
                             _f, _s]),
+    "mvs_pyramid_images": (_i, [_f, _pp, _i, _i, _i, _i, _s]),
+    "mvs_pyramid_record_rows": (_i, [_i, _i, _i]),
+    "mvs_conv2d_lrelu_fwd_packed": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _fl, _s]),
+    "mvs_conv2d_pack_dgrad_weights_batch": (_i, [_i, _pp, _pp, C.POINTER(_i), C.POINTER(_i), _s]),
+    "mvs_conv2d_dgrad_lrelu_mask": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _fl, _i, _i, _s]),
+    "mvs_pyramid_head_mask": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _fl, _s]),
+    "mvs_pyramid_grad_finish": (_i, [_i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _i, _pp, _pp, C.POINTER(_i), _pp, _pp, _s]),
+    "mvs_pyramid_workspace_floats": (_ll, [_i, _i, _i, _i]),
+    "mvs_pyramid_fwd": (_i, [_i, _i, _i, _i, _f, _pp, _pp, C.POINTER(_i), _fl, _pp, _pp, _f, _s]),
+    "mvs_pyramid_bwd": (_i, [_i, _i, _i, _i, _pp, C.POINTER(_i), _fl, _pp, _pp, _pp, _pp, _pp, _f, _s]),
     "mvs_conv2d_dgrad_wl": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     "mvs_conv2d_fwd_wl": (_i, [_f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     "mvs_version": (_i, []),

@@ -30,6 +30,9 @@ struct Conv2dArgs {
                                         //   block's BACKWARD statistics (sum dyh, sum dyh * xhat) instead of (sum y, sum y^2)
     const float* in_stats;              // XF kernels: x is the RAW output of the BatchNorm block in front; [group][4][Cin] (mean, invstd, scale,
                                         //   shift: mvs_bn_finalize_slots) -- relu(x * scale + shift) is applied while the halo is staged
+    float* rec;                         // LM kernels (an input gradient that completes the output gradient of the conv + LeakyReLU block in front):
+                                        //   `bn_raw` is that block's saved OUTPUT [N,YH,YW,Cout], `slope` its negative slope; rec [workgroup
+                                        //   (blockIdx.x)][Cout]: per-channel sums of the masked values this workgroup stored (plain stores)
 };
 
 template <int KS, int S>
@@ -124,6 +127,7 @@ struct Pack2dItem {
     const float* w;
     float* wp;
     int NT, CC, Cin, Cout, NB, pp, wcl, total;
+    int tr;       // 1: the image of a stride-1 layer's INPUT GRADIENT (weights transposed and flipped; Cin / Cout are those of the pass over gy)
 };
 #define MVS_PACK2D_BATCH_MAX 16
 struct Pack2dBatch {
@@ -133,7 +137,7 @@ __global__ __launch_bounds__(256) void conv2d_pack_batch_kernel(Pack2dBatch pb) 
     const Pack2dItem& p = pb.it[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= p.total) return;
-    conv2d_pack_item(p.w, p.wp, p.NT, p.CC, p.Cin, p.Cout, p.NB, 0, -1, p.pp, p.wcl, idx);
+    conv2d_pack_item(p.w, p.wp, p.NT, p.CC, p.Cin, p.Cout, p.NB, p.tr, -1, p.pp, p.wcl, idx);
 }
 
 // STATS: the workgroup also adds the per-channel sum and sum of squares of its outputs into a BatchNorm statistic slot row of its
@@ -146,9 +150,16 @@ __global__ __launch_bounds__(256) void conv2d_pack_batch_kernel(Pack2dBatch pb) 
 // S2D (round 6): the input gradient of a 5x5 stride-2 layer, all four output-parity classes in ONE launch (class = blockIdx.z): a 3x3
 // stride-1 pass over gy on the coarse grid per class with the class's COMPACTED tap list (conv2d_pack_s2d_kernel); a.py / a.px / a.wp are
 // replaced by the class's.  Rounds 2-5 issued four pack launches + four passes of nine taps each.
-template <int KS, int S, int CC, int NB, bool PP = false, bool STATS = false, bool XF = false, bool BST = false, bool S2D = false>
+// LM: the input gradient of a layer of the feature pyramid (jdacs-ms/models/network.py:16-41), whose result is multiplied by the
+// LeakyReLU mask of the block in front (y_front > 0 ? 1 : slope; y_front = a.bn_raw, requested before the first store like BST's raw
+// values) -- what is stored is that block's complete output gradient, and its per-channel sums over the workgroup's tile, the
+// block's bias-gradient partials, go to a.rec [blockIdx.x][Cout] with plain stores: every workgroup writes its row, nothing is zeroed.
+template <int KS, int S, int CC, int NB, bool PP = false, bool STATS = false, bool XF = false, bool BST = false, bool S2D = false,
+          bool LM = false>
 __global__ __launch_bounds__(256) void conv2d_igemm_kernel(Conv2dArgs a) {
     using G = Geo2<KS, S>;
+    static_assert(!LM || (KS == 3 && S == 1 && !PP && !STATS && !XF && !BST && !S2D), "LM: the plain 3x3 stride-1 pass");
+    constexpr bool RAWL = BST || LM;                     // the epilogue reads a tensor shaped like its result
     static_assert(!PP || (KS == 3 && S == 1 && NB == 1), "pixel pairs: 3x3 stride 1, one column tile");
     static_assert(!S2D || (KS == 3 && S == 1 && !PP && !STATS && !XF && !BST), "S2D: the plain 3x3 stride-1 pass");
     constexpr int NTK = PP ? 12 : G::NT;                 // taps the K dimension walks
@@ -303,8 +314,8 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(Conv2dArgs a) {
             }
     }
     const bool vec = (a.Cout & 3) == 0;            // (a 1- or 3-channel output layer takes the scalar stores)
-    float4 rawv[BST ? MBW : 1][BST ? NB : 1];
-    if (BST) {      // ALL requested before the first store (a load written after a store waits for it: the stores may alias as far as hipcc knows)
+    float4 rawv[RAWL ? MBW : 1][RAWL ? NB : 1];
+    if (RAWL) {     // ALL requested before the first store (a load written after a store waits for it: the stores may alias as far as hipcc knows)
 #pragma unroll
         for (int mb = 0; mb < MBW; ++mb)
 #pragma unroll
@@ -336,13 +347,15 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(Conv2dArgs a) {
             for (int r = 0; r < 4; ++r) {
                 float v = acc[mb][nb][r] + ((a.bias && co0 + r < a.Cout) ? a.bias[co0 + r] : 0.f);
                 if (a.act) v = v > 0.f ? v : v * a.slope;
+                const float rw = !RAWL ? 0.f : (r == 0 ? rawv[RAWL ? mb : 0][RAWL ? nb : 0].x : (r == 1 ? rawv[RAWL ? mb : 0][RAWL ? nb : 0].y : (r == 2 ? rawv[RAWL ? mb : 0][RAWL ? nb : 0].z : rawv[RAWL ? mb : 0][RAWL ? nb : 0].w)));
+                if (LM) v = rw > 0.f ? v : v * a.slope;      // (ATen's leaky_relu_backward, to the bit)
                 ov[r] = v;
                 if (co0 + r < a.Cout) {
                     if (BST) {
-                        const float rw = r == 0 ? rawv[BST ? mb : 0][BST ? nb : 0].x : (r == 1 ? rawv[BST ? mb : 0][BST ? nb : 0].y : (r == 2 ? rawv[BST ? mb : 0][BST ? nb : 0].z : rawv[BST ? mb : 0][BST ? nb : 0].w));
                         const float d1 = (rw * bsc[BST ? nb : 0][r] + bsh[BST ? nb : 0][r] > 0.f) ? v : 0.f;
                         st1[nb][r] += d1; st2[nb][r] = fmaf(d1, (rw - bmean[BST ? nb : 0][r]) * binv[BST ? nb : 0][r], st2[nb][r]);
                     } else if (STATS) { st1[nb][r] += v; st2[nb][r] = fmaf(v, v, st2[nb][r]); }
+                    else if (LM) st1[nb][r] += v;
                 }
             }
             if (vec) *reinterpret_cast<float4*>(o + co0) = make_float4(ov[0], ov[1], ov[2], ov[3]);
@@ -382,6 +395,25 @@ __global__ __launch_bounds__(256) void conv2d_igemm_kernel(Conv2dArgs a) {
             if (co < a.Cout)
                 MVS_GLOBAL_ATOMIC_ADD_F64(a.slots + (((size_t)(n / a.imgs_per_group) * a.nslots + (blockIdx.x & (a.nslots - 1))) * 2 + stat) * a.Cout + co,
                                           (double)t);
+        }
+    }
+    if constexpr (LM) {
+        // the same butterfly over the 16 positions of a lane group, then the four waves in a fixed order; pixels outside the image
+        // added nothing.  Row blockIdx.x, columns [16 nb0, 16 (nb0 + NB)) of the record buffer are this workgroup's alone.
+        __shared__ float redm[4 * NB * 16];
+#pragma unroll
+        for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float s1 = st1[nb][r];
+                s1 += __shfl_xor(s1, 1); s1 += __shfl_xor(s1, 2); s1 += __shfl_xor(s1, 4); s1 += __shfl_xor(s1, 8);
+                if (l15 == 0) redm[(wave * NB + nb) * 16 + 4 * g + r] = s1;
+            }
+        __syncthreads();
+        if (tid < NB * 16) {
+            const float t = ((redm[tid] + redm[NB * 16 + tid]) + redm[2 * NB * 16 + tid]) + redm[3 * NB * 16 + tid];
+            const int co = nb0 * 16 + tid;
+            if (co < a.Cout) a.rec[(size_t)blockIdx.x * a.Cout + co] = t;
         }
     }
 }
@@ -1211,6 +1243,83 @@ extern "C" int mvs_conv2d_dgrad_wl(const float* gy, const float* w, float* gx, f
     return mvs_check_launch("conv2d_dgrad_s2");
 }
 
+// ---- the pieces of the feature pyramid's one-node passes that are igemm launches (driver: csrc/feature_pass.cpp) ----------------
+// conv + bias + LeakyReLU with the forward weight image already in `packed` (mvs_conv2d_pack_weights_batch): the pyramid packs its
+// nine layers once per pass for all levels
+extern "C" int mvs_conv2d_lrelu_fwd_packed(const float* x, float* packed, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                                           float negative_slope, hipStream_t stream) {
+    int rc = c2_check("conv2d_lrelu_fwd_packed", N, H, W, Cin, Cout, 3, 1);
+    if (rc) return rc;
+    MVS_REQUIRE(x && packed && y, MVS_ERR_NULL, "conv2d_lrelu_fwd_packed: null pointer argument");
+    return c2_run_igemm(x, nullptr, bias, y, packed, N, H, W, Cin, Cout, 3, 1, 0, stream, 1, negative_slope, nullptr, 0, 1, 1);
+}
+
+// rows of the record buffers of one pyramid level: one per workgroup of the masked input gradient (an 8 x 32 tile of one image)
+extern "C" int mvs_pyramid_record_rows(int N, int H, int W) {
+    if (N < 1 || H < 1 || W < 1) return -1;
+    const long long r = (long long)N * mvs_cdiv(H, 8) * mvs_cdiv(W, 32);
+    return r > 0x7fffffffLL ? -1 : (int)r;
+}
+
+// the masked input gradient is instantiated for the plain (not pixel-pair) form: layers with more than 8 channels on both sides
+static bool c2_lm_served(int Cin, int Cout) { return Cin >= 9 && Cout >= 9 && (Cin <= 32 || Cin == 64) && (Cout <= 32 || Cout == 64); }
+
+// the input-gradient weight images (transposed, flipped) of n 3x3 stride-1 layers in ONE launch: shapes[n][2] = the LAYER's Cin, Cout;
+// ws[i] >= mvs_conv2d_workspace_floats(1, ..., Cin, Cout, 3, 1) floats
+extern "C" int mvs_conv2d_pack_dgrad_weights_batch(int n, const float* const* w, float* const* ws, const int* shapes, const int* w_channels_last,
+                                                   hipStream_t stream) {
+    MVS_REQUIRE(w && ws && shapes && w_channels_last, MVS_ERR_NULL, "conv2d_pack_dgrad_weights_batch: null pointer argument");
+    MVS_REQUIRE(n >= 1 && n <= MVS_PACK2D_BATCH_MAX, MVS_ERR_SHAPE, "conv2d_pack_dgrad_weights_batch: 1..%d layers, got %d", MVS_PACK2D_BATCH_MAX, n);
+    Pack2dBatch pb = {};
+    int maxtotal = 0;
+    for (int i = 0; i < n; ++i) {
+        const int Cin = shapes[2 * i], Cout = shapes[2 * i + 1];
+        int rc = c2_check("conv2d_pack_dgrad_weights_batch", 1, 1, 1, Cin, Cout, 3, 1);
+        if (rc) return rc;
+        MVS_REQUIRE(c2_lm_served(Cin, Cout), MVS_ERR_UNSUPPORTED, "conv2d_pack_dgrad_weights_batch: layer %d (%d -> %d channels) needs more than 8 channels on both sides", i, Cin, Cout);
+        MVS_REQUIRE(w[i] && ws[i], MVS_ERR_NULL, "conv2d_pack_dgrad_weights_batch: null pointer in entry %d", i);
+        Pack2dItem& it = pb.it[i];
+        it.w = w[i]; it.wp = ws[i]; it.wcl = w_channels_last[i] ? 1 : 0; it.tr = 1; it.pp = 0;
+        it.NT = 9; it.CC = c2_cc(3, Cout); it.Cin = Cout; it.Cout = Cin; it.NB = mvs_cdiv(Cin, 16);      // the pass over gy: Cout -> Cin
+        it.total = mvs_cdiv(Cout, it.CC) * c2_ksteps(9, it.CC) * it.NB * 256;
+        if (it.total > maxtotal) maxtotal = it.total;
+    }
+    MVS_LAUNCH(conv2d_pack_batch_kernel, dim3(mvs_cdiv(maxtotal, 256), n), dim3(256), 0, stream, pb);
+    return mvs_check_launch("conv2d_pack_dgrad_weights_batch");
+}
+
+static const char* const C2_LM_LABEL[2][2] = {{"conv2d_igemm k3 cc16 nb1 lrelu-mask", "conv2d_igemm k3 cc16 nb2 lrelu-mask"},
+                                              {"conv2d_igemm k3 cc32 nb1 lrelu-mask", "conv2d_igemm k3 cc32 nb2 lrelu-mask"}};
+
+// Input gradient of a 3x3 stride-1 layer of the pyramid whose gx is the COMPLETE output gradient of the conv + LeakyReLU block in front:
+// gx = dgrad(gy) * (y_front > 0 ? 1 : slope), y_front [N,H,W,Cin] that block's saved output; rec [mvs_pyramid_record_rows(N,H,W)][Cin]
+// receives the per-workgroup channel sums of gx (the block's bias-gradient partials; every row is written, no atomics).
+// ws_packed = 1: ws holds the layer's image from mvs_conv2d_pack_dgrad_weights_batch; w is not read then.
+extern "C" int mvs_conv2d_dgrad_lrelu_mask(const float* gy, const float* w, const float* y_front, float* gx, float* rec, float* ws, int N, int H,
+                                           int W, int Cin, int Cout, float slope, int w_channels_last, int ws_packed, hipStream_t stream) {
+    int rc = c2_check("conv2d_dgrad_lrelu_mask", N, H, W, Cin, Cout, 3, 1);
+    if (rc) return rc;
+    MVS_REQUIRE(gy && (w || ws_packed) && y_front && gx && rec && ws, MVS_ERR_NULL, "conv2d_dgrad_lrelu_mask: null pointer argument");
+    MVS_REQUIRE(c2_lm_served(Cin, Cout), MVS_ERR_UNSUPPORTED, "conv2d_dgrad_lrelu_mask: %d -> %d channels not served (more than 8 on both sides)", Cin, Cout);
+    MVS_REQUIRE(slope > 0.f, MVS_ERR_SHAPE, "conv2d_dgrad_lrelu_mask: the mask is read from the block's output, which needs a positive slope, got %g", (double)slope);
+    MVS_REQUIRE(mvs_pyramid_record_rows(N, H, W) > 0, MVS_ERR_SHAPE, "conv2d_dgrad_lrelu_mask: bad shape N=%d H=%d W=%d", N, H, W);
+    Conv2dArgs a = {};
+    a.x = gy; a.y = gx; a.N = N; a.Hi = H; a.Wi = W; a.Cin = Cout; a.Cout = Cin; a.Ho = H; a.Wo = W;
+    a.os = 1; a.YH = H; a.YW = W; a.nth = mvs_cdiv(H, 8); a.ntw = mvs_cdiv(W, 32); a.nb_total = mvs_cdiv(Cin, 16);
+    a.imgs_per_group = 1; a.slope = slope; a.bn_raw = y_front; a.rec = rec;
+    const int cc = c2_cc(3, Cout), total = mvs_cdiv(Cout, cc) * c2_ksteps(9, cc) * a.nb_total * 256;      // cc: 16 or 32
+    const int nb = a.nb_total <= 2 ? a.nb_total : 2;
+    if (!ws_packed)
+        MVS_LAUNCH(conv2d_pack_kernel, dim3(mvs_cdiv(total, 256)), dim3(256), 0, stream, w, ws, 9, cc, Cout, Cin, a.nb_total, 1, total, -1, 0, w_channels_last ? 1 : 0);
+    a.wp = ws;
+    dim3 grid(N * a.nth * a.ntw, a.nb_total / nb);
+    if (cc == 16 && nb == 1) MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 16, 1, false, false, false, false, false, true>), grid, dim3(256), 0, stream, a);
+    else if (cc == 16) MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 16, 2, false, false, false, false, false, true>), grid, dim3(256), 0, stream, a);
+    else if (nb == 1) MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 32, 1, false, false, false, false, false, true>), grid, dim3(256), 0, stream, a);
+    else MVS_LAUNCH((conv2d_igemm_kernel<3, 1, 32, 2, false, false, false, false, false, true>), grid, dim3(256), 0, stream, a);
+    return mvs_check_launch(C2_LM_LABEL[cc == 16 ? 0 : 1][nb - 1]);
+}
+
 template <int KS, int S, int CXP, int NB>
 static void c2_wgrad_launch(const Wgrad2dArgs& a, int groups, hipStream_t st) {
     constexpr int MT = (KS * KS * CXP + 63) / 64;
@@ -1630,3 +1739,4 @@ extern "C" int mvs_conv_trunk_fwd(int n, const MvsTrunkLayer* layers, const floa
 
 // ---- RefineNet head and tail (refine_kernels.h): input assembly, one-channel BatchNorm + ReLU + residual, folded eval tail ----
 #include "refine_kernels.h"
+#include "pyramid_kernels.h"   // the feature pyramid of CVP-MVSNet as one autograd node: image pyramid, head mask, gradient finish

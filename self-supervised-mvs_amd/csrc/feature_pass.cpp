@@ -332,3 +332,159 @@ extern "C" int mvs_refine_bwd(int frozen, int B, int H, int W, int h, int wd, co
     MVS_TRY(mvs_conv2d_wgrad(y2, draw[3], gw[3], wgrad_ws, B, h, wd, 32, 1, 3, 1, stream));
     return mvs_refine_assemble_bwd(gx0, gout, gimg, gdepth, B, H, W, h, wd, stream);
 }
+
+// ---- FeaturePyramid of CVP-MVSNet (jdacs-ms/models/network.py:16-50) in training, one C call per pass --------------------------------
+// Nine conv 3x3 + bias + LeakyReLU blocks (3 -> 64 -> 64 -> 64 -> 32 -> 32 -> 32 -> 16 -> 16 -> 16), the same weights on S levels of a
+// half-size image pyramid; all views are one batch of N images.  Kernels: csrc/pyramid_kernels.h and the igemm family of csrc/conv2d.hip.
+// One stream, no allocation, no host synchronisation, no events.  `ws`: mvs_pyramid_workspace_floats(N, H, W, S) floats, laid out by
+// pyr_plan below (the forward pass uses only the forward weight images; a pass may be given a fresh buffer).
+extern "C" {
+int mvs_pyramid_images(const float* img, float* const* out, int N, int H, int W, int S, hipStream_t stream);
+int mvs_pyramid_record_rows(int N, int H, int W);
+int mvs_pyramid_head_mask(const float* gout, const float* y, float* g, float* rec, int N, int H, int W, int C, float slope, hipStream_t stream);
+int mvs_pyramid_grad_finish(int nlayers, const int* cin, const int* cout, const int* w_channels_last, int nlevels, const float* const* slots,
+                            const float* const* rec, const int* rows, float* const* gw, float* const* gb, hipStream_t stream);
+int mvs_conv2d_lrelu_fwd_packed(const float* x, float* packed, const float* bias, float* y, int N, int H, int W, int Cin, int Cout,
+                                float negative_slope, hipStream_t stream);
+int mvs_conv2d_pack_dgrad_weights_batch(int n, const float* const* w, float* const* ws, const int* shapes, const int* w_channels_last,
+                                        hipStream_t stream);
+int mvs_conv2d_dgrad_lrelu_mask(const float* gy, const float* w, const float* y_front, float* gx, float* rec, float* ws, int N, int H, int W,
+                                int Cin, int Cout, float slope, int w_channels_last, int ws_packed, hipStream_t stream);
+long long mvs_conv2d_workspace_floats(int op, int N, int H, int W, int Cin, int Cout, int ks, int stride);
+}
+
+#define MVS_PYR_LAYERS 9
+#define MVS_PYR_MAX_LEVELS 6
+static const int PYR_CIN[MVS_PYR_LAYERS] = {3, 64, 64, 64, 32, 32, 32, 16, 16}, PYR_COUT[MVS_PYR_LAYERS] = {64, 64, 64, 32, 32, 32, 16, 16, 16};
+
+struct PyrPlan {                      // offsets in floats into `ws`
+    int h[MVS_PYR_MAX_LEVELS], w[MVS_PYR_MAX_LEVELS], rows[MVS_PYR_MAX_LEVELS];
+    long long fpk[MVS_PYR_LAYERS];    // forward weight images
+    long long dpk[MVS_PYR_LAYERS];    // input-gradient weight images of layers 1 .. 8
+    long long buf[2];                 // ping-pong gradient buffers [N,H,W,64] of the largest level
+    long long slot[MVS_PYR_MAX_LEVELS][MVS_PYR_LAYERS];   // weight-gradient image of (level, layer)
+    long long rec[MVS_PYR_MAX_LEVELS][MVS_PYR_LAYERS];    // bias-gradient records [rows][Cout] of (level, layer)
+    long long wgws;                   // partial images of one mvs_conv2d_wgrad
+    long long total;
+};
+
+// the chain (channel counts connect, every layer served by the kernels it will meet) and the levels, before the first launch
+static int pyr_plan(const char* what, int S, int N, int H, int W, PyrPlan& p) {
+    MVS_REQUIRE(S >= 1 && S <= MVS_PYR_MAX_LEVELS, MVS_ERR_SHAPE, "%s: 1..%d pyramid levels, got %d", what, MVS_PYR_MAX_LEVELS, S);
+    MVS_REQUIRE(N >= 1 && H >= 1 && W >= 1 && (long long)N * H * W * 64 < (1LL << 31), MVS_ERR_SHAPE, "%s: bad image batch [%d,3,%d,%d]", what, N, H, W);
+    long long off = 0;
+    auto take = [&](long long n) { const long long o = off; off += (n + 63) / 64 * 64; return o; };
+    long long wg = 0;
+    for (int i = 0; i < MVS_PYR_LAYERS; ++i) {
+        MVS_REQUIRE(i == 0 || PYR_CIN[i] == PYR_COUT[i - 1], MVS_ERR_SHAPE, "%s: layer %d does not read layer %d's output", what, i, i - 1);
+        const long long f = mvs_conv2d_workspace_floats(0, N, H, W, PYR_CIN[i], PYR_COUT[i], 3, 1);
+        const long long d = i > 0 ? mvs_conv2d_workspace_floats(1, N, H, W, PYR_CIN[i], PYR_COUT[i], 3, 1) : 0;
+        const long long g = mvs_conv2d_workspace_floats(2, N, H, W, PYR_CIN[i], PYR_COUT[i], 3, 1);
+        MVS_REQUIRE(f > 0 && d >= 0 && g > 0 && (i == 0 || (PYR_CIN[i] >= 9 && PYR_COUT[i] >= 9)), MVS_ERR_UNSUPPORTED,
+                    "%s: layer %d (%d -> %d channels) is not served", what, i, PYR_CIN[i], PYR_COUT[i]);
+        p.fpk[i] = take(f);
+        p.dpk[i] = take(d);
+        if (g > wg) wg = g;
+    }
+    p.buf[0] = take((long long)N * H * W * 64);
+    p.buf[1] = take((long long)N * H * W * 64);
+    int h = H, w = W;
+    for (int s = 0; s < S; ++s) {
+        MVS_REQUIRE(h >= 1 && w >= 1, MVS_ERR_SHAPE, "%s: level %d of a %dx%d image has no pixels (%dx%d)", what, s, H, W, h, w);
+        p.h[s] = h; p.w[s] = w; p.rows[s] = mvs_pyramid_record_rows(N, h, w);
+        for (int i = 0; i < MVS_PYR_LAYERS; ++i) {
+            p.slot[s][i] = take((long long)PYR_COUT[i] * PYR_CIN[i] * 9);
+            p.rec[s][i] = take((long long)p.rows[s] * PYR_COUT[i]);
+        }
+        h /= 2; w /= 2;
+    }
+    p.wgws = take(wg);
+    p.total = off;
+    return MVS_OK;
+}
+
+extern "C" long long mvs_pyramid_workspace_floats(int N, int H, int W, int S) {
+    PyrPlan p;
+    return pyr_plan("mvs_pyramid_workspace_floats", S, N, H, W, p) == MVS_OK ? p.total : -1;
+}
+
+static int pyr_ptrs(const char* what, const void* const* p, int n, const char* name) {
+    MVS_REQUIRE(p, MVS_ERR_NULL, "%s: null pointer argument (%s)", what, name);
+    for (int i = 0; i < n; ++i) MVS_REQUIRE(p[i], MVS_ERR_NULL, "%s: %s[%d] is null", what, name, i);
+    return MVS_OK;
+}
+#define PYR_PN(what, p, n) MVS_TRY(pyr_ptrs(what, (const void* const*)(p), n, #p))
+
+// img [N,3,H,W] contiguous -> imgs[s] [N,h_s,w_s,3] (the level images, kept by the caller for the backward pass) and act[s * 9 + i]
+// [N,h_s,w_s,Cout_i] (block i's output on level s; act[s * 9 + 8] is the level's feature map).  w[i] [Cout][Cin][3][3], or
+// channels-last in memory where w_channels_last[i]; bias[i] [Cout].  Launches: pyramid_images, ONE pack launch for the nine forward
+// weight images, 9 S convolutions.
+extern "C" int mvs_pyramid_fwd(int S, int N, int H, int W, const float* img, const float* const* w, const float* const* bias,
+                               const int* w_channels_last, float slope, float* const* imgs, float* const* act, float* ws, hipStream_t stream) {
+    PyrPlan p;
+    MVS_TRY(pyr_plan("mvs_pyramid_fwd", S, N, H, W, p));
+    MVS_REQUIRE(img && w_channels_last && ws, MVS_ERR_NULL, "mvs_pyramid_fwd: null pointer argument");
+    MVS_REQUIRE(slope > 0.f, MVS_ERR_SHAPE, "mvs_pyramid_fwd: the backward pass reads the activation's mask from the outputs, which needs a positive slope, got %g", (double)slope);
+    PYR_PN("mvs_pyramid_fwd", w, MVS_PYR_LAYERS); PYR_PN("mvs_pyramid_fwd", bias, MVS_PYR_LAYERS);
+    PYR_PN("mvs_pyramid_fwd", imgs, S); PYR_PN("mvs_pyramid_fwd", act, S * MVS_PYR_LAYERS);
+    MVS_TRY(mvs_pyramid_images(img, imgs, N, H, W, S, stream));
+    float* packed[MVS_PYR_LAYERS];
+    int shapes[4 * MVS_PYR_LAYERS];
+    for (int i = 0; i < MVS_PYR_LAYERS; ++i) {
+        packed[i] = ws + p.fpk[i];
+        shapes[4 * i] = PYR_CIN[i]; shapes[4 * i + 1] = PYR_COUT[i]; shapes[4 * i + 2] = 3; shapes[4 * i + 3] = 1;
+    }
+    MVS_TRY(mvs_conv2d_pack_weights_batch(MVS_PYR_LAYERS, w, packed, shapes, w_channels_last, stream));
+    for (int s = 0; s < S; ++s)
+        for (int i = 0; i < MVS_PYR_LAYERS; ++i)
+            MVS_TRY(mvs_conv2d_lrelu_fwd_packed(i == 0 ? imgs[s] : act[s * MVS_PYR_LAYERS + i - 1], packed[i], bias[i], act[s * MVS_PYR_LAYERS + i], N,
+                                                p.h[s], p.w[s], PYR_CIN[i], PYR_COUT[i], slope, stream));
+    return MVS_OK;
+}
+
+// gout[s] [N,h_s,w_s,16] or NULL (a level without a gradient contributes nothing and launches nothing) -> gw[i] (the parameter's
+// memory layout) and gb[i] [Cout] of all nine layers; a NULL gw[i] / gb[i] is not computed.  Launches: ONE pack launch for the eight
+// input-gradient weight images; per level with a gradient the head (mask of block 8), then from layer 8 down to 1 the layer's weight
+// gradient (mvs_conv2d_wgrad into the (level, layer) slot) and its masked input gradient into the other ping-pong buffer, then layer
+// 0's weight gradient on the level image; ONE pyramid_grad_finish.
+extern "C" int mvs_pyramid_bwd(int S, int N, int H, int W, const float* const* w, const int* w_channels_last, float slope,
+                               const float* const* imgs, const float* const* act, const float* const* gout, float* const* gw, float* const* gb,
+                               float* ws, hipStream_t stream) {
+    PyrPlan p;
+    MVS_TRY(pyr_plan("mvs_pyramid_bwd", S, N, H, W, p));
+    MVS_REQUIRE(w_channels_last && gout && gw && gb && ws, MVS_ERR_NULL, "mvs_pyramid_bwd: null pointer argument");
+    MVS_REQUIRE(slope > 0.f, MVS_ERR_SHAPE, "mvs_pyramid_bwd: the activation's mask is read from the outputs, which needs a positive slope, got %g", (double)slope);
+    PYR_PN("mvs_pyramid_bwd", w, MVS_PYR_LAYERS); PYR_PN("mvs_pyramid_bwd", imgs, S); PYR_PN("mvs_pyramid_bwd", act, S * MVS_PYR_LAYERS);
+    float* dpk[MVS_PYR_LAYERS - 1];
+    int dshapes[2 * (MVS_PYR_LAYERS - 1)];
+    for (int i = 1; i < MVS_PYR_LAYERS; ++i) {
+        dpk[i - 1] = ws + p.dpk[i];
+        dshapes[2 * (i - 1)] = PYR_CIN[i]; dshapes[2 * (i - 1) + 1] = PYR_COUT[i];
+    }
+    MVS_TRY(mvs_conv2d_pack_dgrad_weights_batch(MVS_PYR_LAYERS - 1, w + 1, dpk, dshapes, w_channels_last + 1, stream));
+    const float* slots[MVS_PYR_MAX_LEVELS * MVS_PYR_LAYERS];
+    const float* recs[MVS_PYR_MAX_LEVELS * MVS_PYR_LAYERS];
+    int rows[MVS_PYR_MAX_LEVELS];
+    for (int s = 0; s < S; ++s) {
+        rows[s] = p.rows[s];
+        const int h = p.h[s], wd = p.w[s];
+        const float* const* a = act + s * MVS_PYR_LAYERS;
+        for (int i = 0; i < MVS_PYR_LAYERS; ++i) {
+            slots[s * MVS_PYR_LAYERS + i] = (gout[s] && gw[i]) ? ws + p.slot[s][i] : nullptr;
+            recs[s * MVS_PYR_LAYERS + i] = gout[s] ? ws + p.rec[s][i] : nullptr;
+        }
+        if (!gout[s]) continue;
+        float* cur = ws + p.buf[0];
+        float* other = ws + p.buf[1];
+        MVS_TRY(mvs_pyramid_head_mask(gout[s], a[MVS_PYR_LAYERS - 1], cur, ws + p.rec[s][MVS_PYR_LAYERS - 1], N, h, wd, PYR_COUT[MVS_PYR_LAYERS - 1], slope,
+                                      stream));
+        for (int i = MVS_PYR_LAYERS - 1; i >= 1; --i) {
+            if (gw[i]) MVS_TRY(mvs_conv2d_wgrad(a[i - 1], cur, ws + p.slot[s][i], ws + p.wgws, N, h, wd, PYR_CIN[i], PYR_COUT[i], 3, 1, stream));
+            MVS_TRY(mvs_conv2d_dgrad_lrelu_mask(cur, nullptr, a[i - 1], other, ws + p.rec[s][i - 1], dpk[i - 1], N, h, wd, PYR_CIN[i], PYR_COUT[i], slope, 0, 1,
+                                                stream));
+            float* t = cur; cur = other; other = t;
+        }
+        if (gw[0]) MVS_TRY(mvs_conv2d_wgrad(imgs[s], cur, ws + p.slot[s][0], ws + p.wgws, N, h, wd, PYR_CIN[0], PYR_COUT[0], 3, 1, stream));
+    }
+    return mvs_pyramid_grad_finish(MVS_PYR_LAYERS, PYR_CIN, PYR_COUT, w_channels_last, S, slots, recs, rows, gw, gb, stream);
+}

@@ -42,7 +42,49 @@ class FeaturePyramid(nn.Module):
             img = getattr(self, name)(img)
         return img
 
+    # The whole pyramid of a TRAINING step as one autograd node (ops.FeaturePyramidFn: one C call per pass, every kernel this
+    # library's, the image pyramid and the bias / weight gradients of all levels included) instead of nine Conv2dLReLUFn nodes per
+    # level.  ON by default by the rule of DESIGN.md section 7: at the training recipe's shape (28 images of 128x160, 2 levels)
+    # forward + backward take 9.35 ms (p10-p90 9.31-9.40) against 9.91 (9.86-9.95), the launch thread 0.96 ms against 2.13
+    # (profiles/pyramid_timing.json).  MVS_HIP_PYRAMID_PASS=0 / FeaturePyramid.hip_pass = False restores the per-layer code below,
+    # which everything the node does not serve takes anyway.
+    hip_pass = os.environ.get("MVS_HIP_PYRAMID_PASS", "1") == "1"
+
+    def hip_pass_slope(self, img):
+        """The common negative slope when this call takes the one-node pass, else None: hip_pass and hip_conv on, fp32 images on the
+        device the library serves that ask for no gradient themselves, autograd on with at least one pyramid parameter asking for
+        one, and the nine blocks the stock ``conv`` blocks (3x3, stride 1, pad 1, bias, LeakyReLU with one common positive slope)."""
+        if not (self.hip_pass and self.hip_conv and img.dtype == torch.float32 and img.dim() == 4 and torch.is_grad_enabled()):
+            return None
+        if img.requires_grad:       # level 0 passes a gradient on to the images (only the resized levels are detached): the node has none
+            return None
+        # (the tests' CPU emulation of the kernels serves CPU images, at seconds per convolution: there only a pyramid whose OWN
+        #  hip_pass has been set takes the node -- the class default is a statement about the device)
+        if not (img.is_cuda or (ops.emulation_active(img) and vars(self).get("hip_pass"))):
+            return None
+        slope, any_grad = None, False
+        for name, cin, cout in _PYRAMID_LAYERS:
+            block = getattr(self, name)
+            if not (isinstance(block, nn.Sequential) and len(block) == 2 and type(block[0]) is nn.Conv2d and type(block[1]) is nn.LeakyReLU):
+                return None
+            c = block[0]
+            if ((c.in_channels, c.out_channels) != (cin, cout) or c.kernel_size != (3, 3) or c.stride != (1, 1) or c.padding != (1, 1)
+                    or c.dilation != (1, 1) or c.groups != 1 or c.bias is None or c.padding_mode != "zeros"):
+                return None
+            if c.weight.dtype != torch.float32 or c.weight.device != img.device or ops._w_layout(c.weight) is None:
+                return None
+            s = float(block[1].negative_slope)
+            if not s > 0.0 or (slope is not None and s != slope):
+                return None
+            slope = s
+            any_grad = any_grad or c.weight.requires_grad or c.bias.requires_grad
+        return slope if any_grad else None
+
     def forward(self, img, scales=5):
+        slope = self.hip_pass_slope(img)
+        if slope is not None and 1 <= scales <= ops.PYRAMID_MAX_LEVELS and min(img.shape[2:]) >> (scales - 1) >= 1:
+            convs = [getattr(self, name)[0] for name, *_ in _PYRAMID_LAYERS]
+            return list(ops.feature_pyramid(img, [c.weight for c in convs], [c.bias for c in convs], slope, scales))
         levels = [self._trunk(img)]
         for _ in range(scales - 1):
             img = F.interpolate(img, scale_factor=0.5, mode='bilinear', align_corners=None).detach()

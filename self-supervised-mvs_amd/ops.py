@@ -2778,6 +2778,145 @@ class Conv2dLReLUFn(torch.autograd.Function):
         return gx, gw, gb, None
 
 
+# ---- FeaturePyramid of CVP-MVSNet (jdacs-ms/models/network.py:16-50) in training as one autograd node: csrc/pyramid_kernels.h +
+# mvs_pyramid_fwd / _bwd ---------------------------------------------------------------------------------------------------------------
+PYRAMID_CH = ((3, 64), (64, 64), (64, 64), (64, 32), (32, 32), (32, 32), (32, 16), (16, 16), (16, 16))
+PYRAMID_MAX_LEVELS = 6
+_PYRAMID_PLANS = {}
+
+
+class _PyramidPlan:
+    """What is the same for every step at one (N, H, W, S): the arena offsets (floats) of the level images and of every block's output."""
+
+    def __init__(self, N, H, W, S):
+        al = lambda v: (v + 63) // 64 * 64
+        self.N, self.H, self.W, self.S = N, H, W, S
+        self.hw, self.img_off, self.act_off = [], [], []
+        off, h, w = 0, H, W
+        for s in range(S):
+            if h < 1 or w < 1:
+                raise ValueError("mvs_amd feature pyramid: level %d of a %dx%d image has no pixels" % (s, H, W))
+            self.hw.append((h, w))
+            self.img_off.append(off); off += al(3 * N * h * w)
+            for _, co in PYRAMID_CH:
+                self.act_off.append(off); off += al(co * N * h * w)
+            h, w = h // 2, w // 2
+        self.floats = off
+        # the gradients of all parameters as one buffer: w0, b0, w1, b1, ...
+        self.g_off, off = [], 0
+        for ci, co in PYRAMID_CH:
+            self.g_off.append((off, off + al(co * ci * 9)))
+            off += al(co * ci * 9) + al(co)
+        self.grad_floats = off
+
+
+def emulation_active(t: torch.Tensor) -> bool:
+    """a library has been loaded that serves tensors on t's device although that is not a GPU (the tests' CPU emulation)"""
+    inst = _lib._INSTANCE
+    return inst is not None and not t.is_cuda and inst.device_type == t.device.type
+
+
+def _pyramid_plan(N, H, W, S):
+    key = (N, H, W, S)
+    plan = _PYRAMID_PLANS.get(key)
+    if plan is None:
+        if len(_PYRAMID_PLANS) > 16:
+            _PYRAMID_PLANS.clear()
+        plan = _PYRAMID_PLANS[key] = _PyramidPlan(N, H, W, S)
+    return plan
+
+
+def _pyramid_ws(lib, plan, like):
+    """the passes' work space, sized right before the call (it follows the library's "wgrad2d_groups" knob)"""
+    nfl = int(lib.raw("mvs_pyramid_workspace_floats", plan.N, plan.H, plan.W, plan.S))
+    if nfl < 0:
+        raise ValueError("mvs_amd feature pyramid: [%d,3,%d,%d] images with %d levels are not served" % (plan.N, plan.H, plan.W, plan.S))
+    return torch.empty(nfl, dtype=torch.float32, device=like.device)
+
+
+class FeaturePyramidFn(torch.autograd.Function):
+    """The nine conv + bias + LeakyReLU blocks of the CVP feature pyramid on every level of the half-size image pyramid as ONE autograd
+    node, one C call per pass (mvs_pyramid_fwd / mvs_pyramid_bwd), every kernel this library's.
+
+    ``img`` [N,3,H,W] fp32 (all views as one batch).  It must not require a gradient: the reference detaches the resized levels but
+    passes level 0's gradient on to the images, which this node does not compute (FeaturePyramid then takes the per-layer path);
+    ``params``: w0, b0, ..., w8, b8 (weights contiguous or channels-last in memory).  Returns ``scales`` feature maps [N,16,h_s,w_s],
+    channels-last in memory: views of the arena that is saved for the backward pass together with the level images."""
+
+    @staticmethod
+    def forward(ctx, img, slope, scales, *params):
+        lib = _lib_for(img)
+        ctx.set_materialize_grads(False)
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError("mvs_amd feature pyramid: images [N,3,H,W] expected, got %s" % (tuple(img.shape),))
+        if ctx.needs_input_grad[0]:
+            raise ValueError("mvs_amd feature pyramid: the one-node pass has no gradient for the images; FeaturePyramid takes the per-layer path for them")
+        if not img.is_contiguous():
+            img = img.contiguous()
+        N, _, H, W = img.shape
+        S = int(scales)
+        if not 1 <= S <= PYRAMID_MAX_LEVELS:
+            raise ValueError("mvs_amd feature pyramid: 1..%d levels, got %d" % (PYRAMID_MAX_LEVELS, S))
+        ws_, bs_ = list(params[0::2]), list(params[1::2])
+        wcl = []
+        for i, ((ci, co), w_, b_) in enumerate(zip(PYRAMID_CH, ws_, bs_)):
+            wl = _w_layout(w_) if tuple(w_.shape) == (co, ci, 3, 3) else None
+            if wl is None or b_ is None or tuple(b_.shape) != (co,) or not b_.is_contiguous():
+                raise ValueError("mvs_amd feature pyramid: block %d needs a dense [%d,%d,3,3] weight and a [%d] bias" % (i, co, ci, co))
+            wcl.append(wl)
+        plan = _pyramid_plan(N, H, W, S)
+        arena = torch.empty(plan.floats, dtype=torch.float32, device=img.device)
+        ws = _pyramid_ws(lib, plan, img)
+        ab = arena.data_ptr()
+        wcl_c = (C.c_int * 9)(*wcl)
+        lib.call("mvs_pyramid_fwd", S, N, H, W, _p(img), _ptr_array(ws_), _ptr_array(bs_), wcl_c, float(slope), _ptrs(ab, plan.img_off),
+                 _ptrs(ab, plan.act_off), _p(ws), _stream(img), tag=("pyramid_fwd:%dx%dx%d:s%d", N, H, W, S))
+        outs = []
+        for s, (h, w) in enumerate(plan.hw):
+            o = plan.act_off[9 * s + 8]
+            outs.append(arena[o:o + 16 * N * h * w].view(N, h, w, 16).permute(0, 3, 1, 2))
+        ctx.plan, ctx.slope, ctx.wcl = plan, float(slope), wcl_c
+        ctx.save_for_backward(arena, *ws_)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gouts):
+        plan = ctx.plan
+        arena, ws_ = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        lib = _lib_for(arena)
+        N, H, W, S = plan.N, plan.H, plan.W, plan.S
+        gouts = [None if g is None else as_cl2(g) for g in gouts]      # (autograd hands over channels-last gradients: no copy)
+        gptr = (C.c_void_p * S)()
+        for s, g in enumerate(gouts):
+            if g is not None:
+                if tuple(g.shape) != (N, 16) + plan.hw[s] or g.dtype != torch.float32:
+                    raise ValueError("mvs_amd feature pyramid: gradient %s of level %d" % (tuple(g.shape), s))
+                gptr[s] = g.data_ptr()
+        grads = torch.empty(plan.grad_floats, dtype=torch.float32, device=arena.device)
+        ws = _pyramid_ws(lib, plan, arena)
+        ab, gb_ = arena.data_ptr(), grads.data_ptr()
+        lib.call("mvs_pyramid_bwd", S, N, H, W, _ptr_array(ws_), ctx.wcl, ctx.slope, _ptrs(ab, plan.img_off), _ptrs(ab, plan.act_off), gptr,
+                 _ptrs(gb_, [o for o, _ in plan.g_off]), _ptrs(gb_, [o for _, o in plan.g_off]), _p(ws), _stream(arena),
+                 tag=("pyramid_bwd:%dx%dx%d:s%d", N, H, W, S))
+        out = [None, None, None]
+        for i, ((ci, co), (wo, bo)) in enumerate(zip(PYRAMID_CH, plan.g_off)):
+            gw = grads[wo:wo + co * ci * 9]
+            gw = gw.view(co, 3, 3, ci).permute(0, 3, 1, 2) if ctx.wcl[i] else gw.view(co, ci, 3, 3)     # the parameter's own strides
+            out.append(gw if ctx.needs_input_grad[3 + 2 * i] else None)
+            out.append(grads[bo:bo + co] if ctx.needs_input_grad[4 + 2 * i] else None)
+        return tuple(out)
+
+
+def feature_pyramid(img, weights, biases, slope, scales):
+    """-> tuple of ``scales`` feature maps [N,16,h_s,w_s] (fp32, channels-last in memory) of the CVP feature pyramid in training:
+    one autograd node, no ATen kernel between the images and the maps or between their gradients and the parameters'."""
+    params = []
+    for w_, b_ in zip(weights, biases):
+        params += [w_, b_]
+    return FeaturePyramidFn.apply(img, float(slope), int(scales), *params)
+
+
 # ------------------------------------------------------------------------------------------------
 # Wide forward 2-D convolutions: the frozen VGG-style trunk in front of the NMF (csrc/conv2d_wide_kernels.h).  Forward only;
 # tensors of this family are PHYSICALLY [N,H,W,C] (contiguous), the layout the NMF reads.
