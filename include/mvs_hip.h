@@ -421,6 +421,27 @@ long long mvs_depth_hypo_workspace_doubles(int B, int H, int W);
 int mvs_depth_hypo(const float* ref_depths, const double* mats, int B, int H, int W, double* ws, float* hypos,
                    hipStream_t stream);
 
+/* ---- the rest of the stage glue of a CVP-MVSNet forward (csrc/cvp_stage_kernels.h) ------------------------------------
+ * mvs_cvp_cameras: every camera product of one forward in ONE launch, label "cvp_cameras" (replaces conditionIntrinsics, _ms_proj +
+ * mvs_relative_projection per level, the host lines of calDepthHypo with their three LU inverses, calSweepingDepthHypo).  fp32
+ * inputs ref_in [B,3,3], src_in [B,S,3,3], ref_ex [B,4,4], src_ex [B,S,4,4], depth_min / depth_max [B] (item 0 is read, like the
+ * reference); level_h: HOST array of the L level heights, level 0 the finest.  1 <= S <= 10, 1 <= L <= 6.  Outputs:
+ *   in_ms  [B,S+1,L,3,3] fp32  rows 0 and 1 of K divided by img_h / level_h[l], row 2 copied; view 0 = reference
+ *   rot    [L,B,S,3,3], trans [L,B,S,3] fp32  of (K_s,l E_s[:3,:] ; 0 0 0 1) (K_ref,l E_ref[:3,:] ; 0 0 0 1)^-1
+ *   mats   [L-1,B,30] fp64  for the levels 0 .. L-2, source view 0, in mvs_depth_hypo's layout (may be NULL when L == 1)
+ *   planes [B,48] fp32  depth_min[0] + i (depth_max[0] - depth_min[0]) / 47
+ * Every product reads the conditioned intrinsics as rounded to fp32 (in_ms), is evaluated in fp64 (Gauss-Jordan with partial
+ * pivoting; a singular matrix gives inf / nan, no error) and rounded once.
+ * mvs_depth_hypo_up: the transition to the next finer level in two launches, labels "depth_hypo_up_interval" and
+ * "depth_hypo_up_write": mvs_depth_hypo on the x2 bilinear up-sampling (F.interpolate(scale_factor=2, align_corners=None)) of
+ * depth [B,h,w], evaluated per fine pixel inside both launches.  hypos [B,8,2h,2w]; depth_up [B,2h,2w] is written when not NULL;
+ * ws: mvs_depth_hypo_workspace_doubles(B, 2h, 2w) doubles.  No atomics: two calls give the same bits. */
+int mvs_cvp_cameras(const float* ref_in, const float* src_in, const float* ref_ex, const float* src_ex, const float* depth_min,
+                    const float* depth_max, int B, int S, int L, int img_h, const int* level_h, float* in_ms, float* rot,
+                    float* trans, double* mats, float* planes, hipStream_t stream);
+int mvs_depth_hypo_up(const float* depth, const double* mats, int B, int h, int w, double* ws, float* hypos, float* depth_up,
+                      hipStream_t stream);
+
 /* ---- SURVEY.md 8(f)-3, first cut (not used by default): the feature extractors' 2-D convolutions ---------------------
  * nn.Conv2d of jdacs/models/module.py:15-22 as used by FeatureNet (jdacs/models/mvsnet.py:17-34): 3x3 stride 1 pad 1 and
  * 5x5 stride 2 pad 2, 1..32 channels, channels-last images x [N,H,W,Cin], w [Cout][Cin][ks][ks], y [N,Ho,Wo,Cout].

@@ -133,6 +133,8 @@ SIGNATURES = {
     "mvs_conv2d_fwd_stats_xf": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _s]),
     "mvs_depth_hypo_workspace_doubles": (_ll, [_i, _i, _i]),
     "mvs_depth_hypo": (_i, [_f, _f, _i, _i, _i, _f, _f, _s]),
+    "mvs_cvp_cameras": (_i, [_f, _f, _f, _f, _f, _f, _i, _i, _i, _i, C.POINTER(_i), _f, _f, _f, _f, _f, _s]),
+    "mvs_depth_hypo_up": (_i, [_f, _f, _i, _i, _i, _f, _f, _f, _s]),
     "mvs_geo_consistency": (_i, [_f, C.POINTER(C.c_void_p), _f, _i, _i, _i, _fl, _fl, _f, _f, _f, _f, _f, _s]),
     "mvs_fusibile_fuse": (_i, [_f, _f, _f, _f, _i, _i, _i, _i, _i, _fl, _fl, _fl, _i, _i, _f, _s]),
     "mvs_unsup_loss_workspace_floats": (_ll, [_i, _i, _i, _i]),

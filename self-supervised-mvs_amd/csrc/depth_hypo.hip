@@ -100,3 +100,5 @@ extern "C" int mvs_depth_hypo(const float* ref_depths, const double* mats, int B
     MVS_LAUNCH(depth_hypo_write_kernel, dim3(a.nblk, B), dim3(256), 0, stream, a);
     return mvs_check_launch("depth_hypo");
 }
+
+#include "cvp_stage_kernels.h"   // mvs_cvp_cameras, mvs_depth_hypo_up: the stage glue around the two kernels above

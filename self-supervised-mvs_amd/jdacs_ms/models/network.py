@@ -139,6 +139,16 @@ class CVPMVSNet(nn.Module):
     every BatchNorm module) normalises with the running statistics, does not write them, and trains through every layer; ``.eval()``
     with autograd on computes the same step (the reference's eval forward works in place and autograd rejects it; this one does not)."""
     batch_views = os.environ.get("MVS_CVP_BATCH_VIEWS", "1") != "0"   # feature pyramid of all views in one batch
+    # The stage glue between the kernels as this library's launches (csrc/cvp_stage_kernels.h): ops.cvp_cameras once per forward for
+    # every camera product (conditioned intrinsics, rot / trans of every level, calDepthHypo's matrices, the sweeping planes) and
+    # ops.depth_hypotheses_up per refine level (x2 bilinear up-sampling + calDepthHypo in two launches) instead of the ATen launches
+    # and the three solver-library LU inverses per level of the code below.  ON by default by the rule of DESIGN.md section 7, event
+    # time of the whole forward (profiles/cvp_stage_timing.json): at the training recipe's shape (B = 4, nsrc = 6, 128x160, 2 levels,
+    # train mode) 5.21 ms (p10-p90 5.19-5.24) against 5.53 (5.51-5.55), the launch thread 1.04 ms against 2.39; at BASELINE configs[3]
+    # (864x1152, 3 levels, no_grad) 36.03 ms (35.96-36.08) against 36.52 (36.47-36.58), the launch thread 2.33 ms against 4.00.
+    # MVS_HIP_CVP_STAGE=0 / CVPMVSNet.hip_stage = False restores the code below, which 11 or more source views or 7 or more levels
+    # take anyway.
+    hip_stage = os.environ.get("MVS_HIP_CVP_STAGE", "1") == "1"
 
     def __init__(self, args, align_corners=ALIGN_CORNERS):
         super().__init__()
@@ -165,6 +175,8 @@ class CVPMVSNet(nn.Module):
         else:   # network.py:100-105: one pyramid call per view
             ref_fp = self.featurePyramid(ref_img, a.nscale)
             src_fps = [self.featurePyramid(src_imgs[:, i], a.nscale) for i in range(a.nsrc)]
+        if self.hip_stage and 1 <= a.nsrc <= ops.CVP_MAX_SRC and 1 <= a.nscale <= ops.PYRAMID_MAX_LEVELS:
+            return self._forward_stage(ref_img, ref_fp, src_fps, ref_in, src_in, ref_ex, src_ex, depth_min, depth_max)
         ref_in_ms = conditionIntrinsics(ref_in, ref_img.shape, [f.shape for f in ref_fp])
         src_in_ms = torch.stack([conditionIntrinsics(src_in[:, i], ref_img.shape, [f.shape for f in src_fps[i]])
                                  for i in range(a.nsrc)]).permute(1, 0, 2, 3, 4)
@@ -195,6 +207,25 @@ class CVPMVSNet(nn.Module):
             depth_est_list.append(depth)
 
         depth_est_list.reverse()  # [0] is the finest scale (network.py:195)
+        return {"depth_est_list": depth_est_list, "prob_confidence": conf}
+
+    def _forward_stage(self, ref_img, ref_fp, src_fps, ref_in, src_in, ref_ex, src_ex, depth_min, depth_max):
+        """_forward after the feature pyramids with hip_stage on: the same levels, every launch between them this library's"""
+        a = self.args
+        _, rot, trans, mats, planes = ops.cvp_cameras(ref_in, src_in[:, :a.nsrc], ref_ex, src_ex[:, :a.nsrc], depth_min, depth_max,
+                                                      ref_img.shape[2], [f.shape[2] for f in ref_fp], like=ref_fp[-1])
+        depth_est_list = []
+        depth_hypos = planes
+        for level in range(a.nscale - 1, -1, -1):
+            if level < a.nscale - 1:
+                depth_hypos = ops.depth_hypotheses_up(depth, mats[level])
+            cost_volume = ops.plane_sweep_variance(ref_fp[level], [fp[level] for fp in src_fps], rot[level], trans[level], depth_hypos,
+                                                   align_corners=self.align_corners, ms_alias=True)
+            cost_reg = self.cost_reg_refine(cost_volume)
+            del cost_volume
+            depth, conf = ops.softargmin_conf(cost_reg, depth_hypos)
+            depth_est_list.append(depth)
+        depth_est_list.reverse()
         return {"depth_est_list": depth_est_list, "prob_confidence": conf}
 
 

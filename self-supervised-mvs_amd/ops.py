@@ -2518,6 +2518,63 @@ def depth_hypotheses(ref_depths: torch.Tensor, mats: torch.Tensor) -> torch.Tens
     return hypos
 
 
+# ---- the rest of a CVPMVSNet forward's stage glue (csrc/cvp_stage_kernels.h; CVPMVSNet.hip_stage) --------------------------------
+CVP_MAX_SRC = 10          # MVS_MAX_SRC
+CVP_PLANES = 48
+
+
+def cvp_cameras(ref_in, src_in, ref_ex, src_ex, depth_min, depth_max, img_h: int, level_hs: Sequence[int],
+                like: Optional[torch.Tensor] = None):
+    """Every camera product of one CVPMVSNet forward in ONE launch (``mvs_cvp_cameras``) instead of conditionIntrinsics, _ms_proj +
+    relative_projections per level, calDepthHypo's host lines (three fp64 LU inverses of the solver library per level) and
+    calSweepingDepthHypo.  ref_in [B,3,3], src_in [B,S,3,3], ref_ex [B,4,4], src_ex [B,S,4,4], depth_min / depth_max [B];
+    ``level_hs``: the feature maps' heights, finest first.  Returns
+
+      in_ms [B,S+1,L,3,3]  the conditioned intrinsics, view 0 = reference
+      rot [L,B,S,3,3], trans [L,B,S,3]  rot[l] / trans[l] are what ops.plane_sweep_variance takes at level l
+      mats [L-1,B,30] fp64  mats[l] is what ops.depth_hypotheses_up takes for the transition to level l
+      planes [B,48]  the coarse level's sweeping planes
+
+    No gradient, like the reference (no_grad).  The device rules of relative_projections: ``like`` is the feature map the results
+    will be used with; cameras that live elsewhere are copied to its device and other dtypes are cast to fp32.  A device the
+    library does not serve raises (there is no host restatement: the public helpers of jdacs_ms.models.modules are that)."""
+    b, s, nl = ref_in.shape[0], src_in.shape[1] if src_in.dim() == 4 else -1, len(level_hs)
+    if (tuple(ref_in.shape) != (b, 3, 3) or tuple(src_in.shape) != (b, s, 3, 3) or tuple(ref_ex.shape) != (b, 4, 4)
+            or tuple(src_ex.shape) != (b, s, 4, 4) or depth_min.numel() < 1 or depth_max.numel() < 1):
+        raise ValueError("cvp_cameras: need [B,3,3], [B,S,3,3], [B,4,4], [B,S,4,4] and [B] depth ranges, got %s"
+                         % ([tuple(t.shape) for t in (ref_in, src_in, ref_ex, src_ex, depth_min, depth_max)],))
+    if not (1 <= s <= CVP_MAX_SRC and 1 <= nl <= PYRAMID_MAX_LEVELS):
+        raise ValueError("cvp_cameras: 1..%d source views and 1..%d levels, got %d and %d" % (CVP_MAX_SRC, PYRAMID_MAX_LEVELS, s, nl))
+    dev = like.device if like is not None else ref_in.device
+    cams = [t.detach().to(device=dev, dtype=torch.float32).contiguous() for t in (ref_in, src_in, ref_ex, src_ex, depth_min, depth_max)]
+    lib = _lib_for(cams[0])
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    in_ms, rot, trans, planes = new(b, s + 1, nl, 3, 3), new(nl, b, s, 3, 3), new(nl, b, s, 3), new(b, CVP_PLANES)
+    mats = torch.empty((nl - 1, b, 30), dtype=torch.float64, device=dev)
+    lib.call("mvs_cvp_cameras", *[_p(t) for t in cams], b, s, nl, int(img_h), (C.c_int * nl)(*[int(h) for h in level_hs]), _p(in_ms),
+             _p(rot), _p(trans), _p(mats) if nl > 1 else None, _p(planes), _stream(cams[0]))
+    return in_ms, rot, trans, mats, planes
+
+
+def depth_hypotheses_up(depth: torch.Tensor, mats: torch.Tensor, want_depth_up: bool = False):
+    """The transition to the next finer level (``mvs_depth_hypo_up``, two launches): depth [B,h,w] fp32 of the coarser level, mats
+    [B,30] fp64 of the finer one -> hypotheses [B,8,2h,2w] fp32 = F.interpolate(depth, scale_factor=2, mode='bilinear') + k * interval,
+    k = -4..3, as ``depth_hypotheses`` of the up-sampled map; with ``want_depth_up`` also that map [B,2h,2w].  No gradient."""
+    depth = depth.detach().float().contiguous()
+    lib = _lib_for(depth)
+    if depth.dim() != 3:
+        raise ValueError("depth must be [B,h,w], got %s" % (tuple(depth.shape),))
+    b, h, w = depth.shape
+    if mats.dtype != torch.float64 or tuple(mats.shape) != (b, 30) or mats.device != depth.device:
+        raise ValueError("mats must be float64 [B,30] on the depth map's device, got %s %s on %s" % (mats.dtype, tuple(mats.shape), mats.device))
+    mats = mats.contiguous()
+    ws = torch.empty(lib.raw("mvs_depth_hypo_workspace_doubles", b, 2 * h, 2 * w), dtype=torch.float64, device=depth.device)
+    hypos = torch.empty((b, 8, 2 * h, 2 * w), dtype=torch.float32, device=depth.device)
+    up = torch.empty((b, 2 * h, 2 * w), dtype=torch.float32, device=depth.device) if want_depth_up else None
+    lib.call("mvs_depth_hypo_up", _p(depth), _p(mats), b, h, w, _p(ws), _p(hypos), _p(up), _stream(depth))
+    return (hypos, up) if want_depth_up else hypos
+
+
 # ------------------------------------------------------------------------------------------------
 # SURVEY 8(f)-3, first cut (not used by default): the feature extractors' 2-D convolutions
 # ------------------------------------------------------------------------------------------------
